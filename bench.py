@@ -13,6 +13,10 @@ Rank 0 prints ONE JSON line with the whole-job scenes/s plus:
                  taken from this run's rulebooks) / its mean launch duration measured with HIP
                  events on the launch stream, against the 8 TB/s HBM peak;
   cpu_baseline — oracle/ (CPU restatement, "port") timed on this host, 1 thread, bounded sample.
+A plain run times ONE region of exactly --steps steps.  --full adds what takes runs of its own: five
+repetitions of the region (`value` = the median one), the measured HBM traffic of the dominant kernel
+(two rocprofv3 --pmc child passes), batch_sweep, pipelined, the secondary child processes and
+cpu_baseline.  --dump-outputs DIR writes what the last timed step returned (see dump_outputs).
 """
 import argparse
 import json
@@ -33,17 +37,22 @@ def parse():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=5)
-    ap.add_argument("--batch", type=int, default=128, help="scenes per step per GPU (round 4: 128 — the same code gives +3.8 % over 64 on one box: "
+    ap.add_argument("--batch", type=int, default=128, help="scenes per step per GPU (round 4: 128 — the same code gives +3.8 %% over 64 on one box: "
                                                             "the per-launch tails of 59 launches are paid once per twice the rows; 64 stays in batch_sweep)")
     ap.add_argument("--graph", action="store_true", help="replay the forward from a captured hipGraph (small batches "
                                                           "are launch-bound); per-kernel events are not recorded")
     ap.add_argument("--dtype", default="bf16", choices=["bf16", "fp32"])
-    ap.add_argument("--cpu-scenes", type=int, default=8, help="scenes timed through the CPU oracle on ONE thread (0 = skip the CPU baseline)")
+    ap.add_argument("--full", action="store_true", help="also measure what takes runs of its own (see the module docstring); "
+                                                         "a plain run does the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write the outputs of the last one "
+                                                                        "to DIR/<name>.npy (f32 / f64, a seeded sample of rows)")
+    ap.add_argument("--cpu-scenes", type=int, default=8, help="--full: scenes timed through the CPU oracle on ONE thread (0 = skip the CPU baseline)")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads of the all-core CPU leg (0 = every core this job may use: "
                                                               "min(physical cores, sched_getaffinity, cgroup cpu.max))")
-    ap.add_argument("--reps", type=int, default=5, help="repetitions of the timed K-step region; `value` is the median one, the list is reported")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the secondary measurements (fp32 engine, Box Seeker, extraction, training "
-                                                                "step: each a fresh child process)")
+    ap.add_argument("--reps", type=int, default=None, help="repetitions of the timed K-step region; `value` is the median one, the list is "
+                                                           "reported (default 1, 5 with --full)")
+    ap.add_argument("--no-secondary", action="store_true", help="--full: skip the secondary measurements (fp32 engine, Box Seeker, extraction, "
+                                                                "training step: each a fresh child process)")
     ap.add_argument("--secondary-budget", type=float, default=540.0, help="wall-clock seconds all secondary child processes may take together; "
                                                                           "those that do not fit are skipped and say so")
     ap.add_argument("--no-events", action="store_true", help="do not bracket conv launches with events")
@@ -54,10 +63,13 @@ def parse():
                          "are taken inside the timed region; 'graphs' = the same two-graph replay, one batch at a time (rounds 3-5's timed "
                          "step); 'stream' = every kernel a plain stream launch (rounds 1-3's)")
     ap.add_argument("--in-flight", type=int, default=2, help="batches in flight of --launch pipeline")
-    ap.add_argument("--no-traffic", action="store_true", help="do not measure roofline.traffic (two rocprofv3 --pmc child runs of this script, ~1 min); "
-                    "the committed profile's value is quoted then")
-    ap.add_argument("--no-sweep", action="store_true", help="skip the extra small-batch measurements (1 and 8 scenes per step)")
-    return ap.parse_args()
+    ap.add_argument("--no-traffic", action="store_true", help="--full: do not measure roofline.traffic (two rocprofv3 --pmc child runs of this "
+                    "script, ~1 min); the committed profile's value is quoted then, as in a plain run")
+    ap.add_argument("--no-sweep", action="store_true", help="--full: skip the extra small-batch measurements (1 and 8 scenes per step)")
+    args = ap.parse_args()
+    if args.reps is None:
+        args.reps = 5 if args.full else 1
+    return args
 
 
 def algorithmic_bytes(tag, P, n_out, b):
@@ -328,6 +340,38 @@ def measured_traffic(kname, B, dtype, budget_s=110.0):
     return (2.0 * sum(f) / len(f) + sum(w) / len(w)) * 1024.0, min(len(f), len(w))
 
 
+DUMP_ROWS = 32768                 # rows kept per output tensor (every row when it has fewer)
+DUMP_LIMIT_BYTES = 64 * 10 ** 6   # 128 scenes per step: ~52 MB
+
+
+def dump_outputs(res, sparse_shape, out_dir):
+    """--dump-outputs: the dict the timed path returned for its last batch, as out_dir/<name>.npy.  The voxeliser's outputs
+    (voxel_coords [b, z, y, x], voxel_num_points, voxel_features) and, for each SparseConvTensor (x_conv1 .. x_conv4, out),
+    <name>_features and <name>_indices; all float32 (bf16 features and int32 indices convert exactly), plus `counts` (float64,
+    the site count of every stage).  The rows of a tensor are put in (b, z, y, x) order first, so that a build that emits them
+    in another order compares equal, then at most DUMP_ROWS of them are kept at seeded positions: the same rows for the same
+    row count, shared by the arrays of one tensor."""
+    groups = [(res["voxel_coords"], sparse_shape, {k: res[k] for k in ("voxel_coords", "voxel_num_points", "voxel_features")})]
+    for name in ("x_conv1", "x_conv2", "x_conv3", "x_conv4", "out"):
+        t = res[name]
+        groups.append((t.indices, t.spatial_shape, {f"{name}_features": t.features, f"{name}_indices": t.indices}))
+    arrays = {"counts": np.asarray([int(c) for c in res["counts"]], np.float64)}
+    for seed, (idx, shape, members) in enumerate(groups):
+        i = idx.to(torch.int64)
+        order = torch.argsort(((i[:, 0] * shape[0] + i[:, 1]) * shape[1] + i[:, 2]) * shape[2] + i[:, 3], stable=True)
+        n = int(order.shape[0])
+        if n > DUMP_ROWS:
+            keep = np.sort(np.random.default_rng(seed).choice(n, DUMP_ROWS, replace=False))
+            order = order[torch.from_numpy(keep).to(order.device)]
+        for key, t in members.items():
+            arrays[key] = t[order].float().cpu().numpy()
+    total = sum(a.nbytes for a in arrays.values())
+    assert total <= DUMP_LIMIT_BYTES, f"outputs to dump take {total} bytes"
+    os.makedirs(out_dir, exist_ok=True)
+    for key, a in arrays.items():
+        np.save(os.path.join(out_dir, key + ".npy"), a)
+
+
 def main():
     args = parse()
     rank = int(os.environ.get("RANK", "0"))
@@ -481,7 +525,7 @@ def main():
                     res = pipe.result()
         else:
             for _ in range(args.steps):
-                step()
+                res = step()
         barrier()
         t1 = time.perf_counter()
         e = t1 - t0
@@ -498,7 +542,9 @@ def main():
     eng.profile, eng.profile_only = None, None
     if pipe is not None:
         pipe.profile = None
-        counts = res["counts"]
+    counts = res["counts"]          # (of the last timed step)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(res, net.sparse_shape, args.dump_outputs)
 
     # Per-rank shard evidence: every rank's stage counts and a checksum of its voxel coordinates travel to
     # rank 0 in ONE all_gather after the timed region, so that a multi-GPU run can be checked for N DISTINCT shards (rank r takes
@@ -573,12 +619,12 @@ def main():
         srt = ",sorted" if (args.dtype == "bf16" and K == 27 and S.sorted_by_default(cin, cout, torch.bfloat16, int(pts.shape[0] * eng.cap_factor[2]))) else ""
         kname = (f"spconv_mfma_kernel<{cin},{cout},{mb},{K if K == 27 else 0},{win},bf16{srt}>"
                  if args.dtype == "bf16" else f"spconv_mfma_f32_kernel<{cin},{cout},{mb32}>")
-        # HBM bytes per launch of that kernel: MEASURED in the default run (measured_traffic: PMC counters need rocprofv3 around a
+        # HBM bytes per launch of that kernel: MEASURED in a --full run (measured_traffic: PMC counters need rocprofv3 around a
         # process, so this script is started twice more, 3 steps each, as a child of rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE; gfx950
-        # FETCH_SIZE x2 correction applied).  Child runs (--no-secondary, --no-traffic) and a failed measurement quote the committed
-        # passes of the same command (profiles/r0N_pmc_traffic_<dtype>_b<B>.json); null when there is neither
+        # FETCH_SIZE x2 correction applied).  Plain runs, child runs (--no-secondary, --no-traffic) and a failed measurement quote the
+        # committed passes of the same command (profiles/r0N_pmc_traffic_<dtype>_b<B>.json); null when there is neither
         traffic, traffic_src = None, None
-        if rank == 0 and world == 1 and not args.no_traffic and not args.no_secondary and not args.graph:
+        if rank == 0 and world == 1 and args.full and not args.no_traffic and not args.no_secondary and not args.graph:
             try:
                 traffic, n_l = measured_traffic(kname, B, args.dtype)
                 traffic_src = (f"measured in this run: two rocprofv3 --pmc passes (FETCH_SIZE, WRITE_SIZE; --kernel-trace only) of `bench.py --batch {B} --steps 3` "
@@ -642,7 +688,7 @@ def main():
         out["roofline"]["step"] = step_roofline(layers_in_order, int(pts.shape[0]), int(counts[0]), b, args.dtype,
                                                 1e3 * elapsed / args.steps, mfma_peak)
 
-    if rank == 0 and world == 1 and not args.no_sweep and not args.graph:
+    if rank == 0 and world == 1 and args.full and not args.no_sweep and not args.graph:
         # Extra fields (the headline stays `value` at --batch): the same path at 1 and 8 scenes per step — batch size 1 is
         # what the reference's extraction script and configs[0] run — as stream launches and replayed from a hipGraph, both
         # measured HERE, in this process, after the event-timed launches above (round 2 had to move the graph leg into a
@@ -734,7 +780,7 @@ def main():
         except Exception as e:
             out["pipelined"] = {"error": repr(e)[:200]}
 
-    if rank == 0 and world == 1 and not args.no_secondary and not args.graph and args.dtype == "bf16":
+    if rank == 0 and world == 1 and args.full and not args.no_secondary and not args.graph and args.dtype == "bf16":
         # SURVEY 8(d)'s secondary metrics, each from a fresh child process (best effort: never lose the headline over one)
         py, T = sys.executable, os.path.join(ROOT, "tools")
         sec = {}
@@ -774,7 +820,7 @@ def main():
                 sec[name] = {"error": repr(e)[:300]}
         out["secondary"] = sec
 
-    if rank == 0 and world == 1 and args.cpu_scenes > 0:   # (baseline leg: N = 1 only)
+    if rank == 0 and world == 1 and args.full and args.cpu_scenes > 0:   # (baseline leg: N = 1 only)
         out["cpu_baseline"] = cpu_baseline(args, net, syn)
     if rank == 0:
         out.update(flat_summary(out))

@@ -113,7 +113,7 @@ def batch_fixture():
         arrays[k + "_indices"], arrays[k + "_features"] = i, f.astype(np.float32)
         arrays[k + "_spatial_shape"] = np.array(t.spatial_shape, np.int64)
     arrays["state_checksum"] = np.array([float(np.abs(v).astype(np.float64).sum()) for v in sd.values()])
-    np.savez_compressed(os.path.join(HERE, "backbone_forward_batch.npz"), **arrays)
+    T.save_npz_parts(os.path.join(HERE, "backbone_forward_batch.npz"), arrays)
 
 
 if __name__ == "__main__":

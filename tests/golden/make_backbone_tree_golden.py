@@ -67,6 +67,40 @@ def shell(name, path):
     return m
 
 
+PART_LIMIT = 1000 * 1000   # bytes per fixture file (the repository keeps every file under 1 MiB)
+
+
+def save_npz_parts(path, arrays):
+    """np.savez_compressed split over <name>.npz, <name>.part1.npz, ... so that no file exceeds PART_LIMIT bytes
+    (tests/test_backbone_tree.py::_golden merges them).  Arrays go whole, largest compressed size first, into the first
+    file with room."""
+    import io
+    import zlib
+    stem = path[:-len(".npz")]
+
+    def packed(v):
+        buf = io.BytesIO()
+        np.save(buf, np.asanyarray(v))
+        return len(zlib.compress(buf.getvalue())) + 256    # (+ the zip entry's own headers)
+
+    parts = []
+    for k, n in sorted(((k, packed(v)) for k, v in arrays.items()), key=lambda kv: -kv[1]):
+        part = next((p for p in parts if p[0] + n <= PART_LIMIT), None)
+        if part is None:
+            part = [0, {}]
+            parts.append(part)
+        part[0] += n
+        part[1][k] = arrays[k]
+    k = 1
+    while os.path.exists(f"{stem}.part{k}.npz"):       # (parts of an earlier, larger fixture)
+        os.remove(f"{stem}.part{k}.npz")
+        k += 1
+    for i, (_, members) in enumerate(parts):
+        name = path if i == 0 else f"{stem}.part{i}.npz"
+        np.savez_compressed(name, **members)
+        assert os.path.getsize(name) <= PART_LIMIT, name
+
+
 def load_reference():
     """pcdet.models.backbones_3d.spconv_backbone without running the package __init__s (they import the
     whole detector zoo and its compiled ops)."""
@@ -171,7 +205,7 @@ def main():
             arrays[k + "_spatial_shape"] = np.array(t.spatial_shape, np.int64)
         # the weights are a function of (tree, seed); a checksum guards the recipe itself
         arrays["state_checksum"] = np.array([float(np.abs(v).astype(np.float64).sum()) for v in sd.values()])
-        np.savez_compressed(os.path.join(out_dir, "backbone_forward.npz" if res else "backbone_forward_plain.npz"), **arrays)
+        save_npz_parts(os.path.join(out_dir, "backbone_forward.npz" if res else "backbone_forward_plain.npz"), arrays)
 
     with open(os.path.join(out_dir, "backbone_tree.json"), "w") as f:
         json.dump(tree, f, indent=1, sort_keys=True)

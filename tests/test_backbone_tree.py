@@ -27,8 +27,17 @@ TREE = json.load(open(os.path.join(HERE, "golden", "backbone_tree.json")))
 OUTPUTS = ("out", "x_conv1", "x_conv2", "x_conv3", "x_conv4")
 
 
+def _golden(name):
+    """a fixture of tests/golden/make_backbone_*_golden.py: <name>.npz and its <name>.part<k>.npz (save_npz_parts), one dict"""
+    fx, k = dict(np.load(os.path.join(HERE, "golden", name + ".npz"))), 1
+    while os.path.exists(os.path.join(HERE, "golden", f"{name}.part{k}.npz")):
+        fx.update(np.load(os.path.join(HERE, "golden", f"{name}.part{k}.npz")))
+        k += 1
+    return fx
+
+
 def _fixture(plain=False):
-    return np.load(os.path.join(HERE, "golden", "backbone_forward_plain.npz" if plain else "backbone_forward.npz"))
+    return _golden("backbone_forward_plain" if plain else "backbone_forward")
 
 
 def _describe(m):
@@ -292,7 +301,7 @@ def test_load_state_dict_equals_the_reference_adapter_on_every_layout():
 
 
 def _batch_fixture():
-    return np.load(os.path.join(HERE, "golden", "backbone_forward_batch.npz"))
+    return _golden("backbone_forward_batch")
 
 
 def test_batch_recipe_is_the_fixture_and_the_oracle_reproduces_the_reference_on_it():

@@ -1,7 +1,10 @@
 """Parity of the HIP operators (through the C ABI and the reference-named python wrappers) with
-the CPU oracle and, where it could be built, with the reference's own kernels compiled by hipcc
-(oracle/_ref/libref_iou3d_gpu.so).  Integer outputs must be bit-exact."""
+the CPU oracle and with the reference's own kernels compiled by hipcc (oracle/_ref/libref_iou3d_gpu.so,
+where it could be built; their outputs for these inputs are recorded in tests/golden/iou3d_ref_gpu.npz).
+Integer outputs must be bit-exact."""
 import ctypes
+import hashlib
+import os
 
 import numpy as np
 import pytest
@@ -118,24 +121,31 @@ def test_cpu_tensor_is_rejected_not_silently_computed(cuda):
         C.points_in_boxes_gpu(torch.zeros((1, 1, 7)), torch.zeros((1, 1, 3)), torch.zeros((1, 1), dtype=torch.int32))
 
 
+IOU_GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "iou3d_ref_gpu.npz")
+
+
 def _ref_gpu():
+    """the reference's iou3d kernels (oracle/_ref/libref_iou3d_gpu.so), None where they were not built"""
     from oracle import ref_loader
 
-    lib = ref_loader.iou3d_gpu_lib()
-    if lib is None:
-        pytest.skip("oracle/_ref/libref_iou3d_gpu.so not built")
-    return lib
+    return ref_loader.iou3d_gpu_lib()
+
+
+def _iou_gold():
+    """what the reference's kernels returned for the inputs below (tests/golden/make_iou3d_ref_golden.py)"""
+    return np.load(IOU_GOLD)
+
+
+def _sha(*arrays):
+    return hashlib.sha256(b"".join(np.ascontiguousarray(a).tobytes() for a in arrays)).hexdigest()
 
 
 def _p(t):
     return ctypes.c_void_p(t.data_ptr())
 
 
-def test_rotated_iou_bit_exact_vs_reference_kernels(cuda, oracle, rng):
-    """Same GPU, same ocml, same IEEE op sequence -> bit-identical to the reference's kernels."""
-    from findnpropagate_amd.iou3d_nms import iou3d_nms_cuda as C, iou3d_nms_utils as U
-
-    ref = _ref_gpu()
+def iou_inputs(rng):
+    """boxes A (83, 7), B (57, 7) of the rotated-IoU parity test"""
     A = syn.random_boxes(rng, 83, 6.0)
     Bx = syn.random_boxes(rng, 57, 6.0)
     A[:5] = Bx[:5]                                   # identical boxes
@@ -146,25 +156,45 @@ def test_rotated_iou_bit_exact_vs_reference_kernels(cuda, oracle, rng):
     A[7, :] = [0, 0, 0, 4, 2, 1, 0.0]
     Bx[7, :] = [0, 0, 0, 4, 2, 1, np.pi / 2]         # 90 degrees
     A[8, 3:5] = 1e-3                                  # tiny
+    return A, Bx
+
+
+def iou_reference(ref, a, b):
+    """the reference's box_overlap / iou_bev / aligned-overlap kernels on device boxes a (83, 7), b (57, 7)"""
+    ov_ref = torch.zeros((a.shape[0], b.shape[0]), device=a.device)
+    ref.ref_boxes_overlap(a.shape[0], _p(a), b.shape[0], _p(b), _p(ov_ref))
+    iou_ref = torch.zeros_like(ov_ref)
+    ref.ref_boxes_iou_bev(a.shape[0], _p(a), b.shape[0], _p(b), _p(iou_ref))
+    n = b.shape[0]
+    al_ref = torch.zeros((n, 1), device=a.device)
+    ref.ref_boxes_aligned_overlap(n, _p(a[:n].contiguous()), _p(b), _p(al_ref))
+    torch.cuda.synchronize()
+    return {"overlap": ov_ref, "iou_bev": iou_ref, "aligned_overlap": al_ref}
+
+
+def test_rotated_iou_bit_exact_vs_reference_kernels(cuda, oracle, rng):
+    """Same GPU, same ocml, same IEEE op sequence -> bit-identical to the reference's kernels: to their recorded outputs and,
+    where oracle/_ref holds them, to the kernels themselves."""
+    from findnpropagate_amd.iou3d_nms import iou3d_nms_cuda as C, iou3d_nms_utils as U
+
+    A, Bx = iou_inputs(rng)
+    gold = _iou_gold()
+    assert _sha(A, Bx) == str(gold["iou_inputs_sha256"]), "inputs differ from the recorded ones"
     a, b = torch.from_numpy(A).to(cuda), torch.from_numpy(Bx).to(cuda)
     ov = torch.zeros((83, 57), device=cuda)
     C.boxes_overlap_bev_gpu(a, b, ov)
-    ov_ref = torch.zeros_like(ov)
-    ref.ref_boxes_overlap(83, _p(a), 57, _p(b), _p(ov_ref))
-    torch.cuda.synchronize()
-    assert torch.equal(ov, ov_ref), f"max diff {(ov - ov_ref).abs().max().item()}"
     iou = U.boxes_iou_bev(a, b)
-    iou_ref = torch.zeros_like(iou)
-    ref.ref_boxes_iou_bev(83, _p(a), 57, _p(b), _p(iou_ref))
-    torch.cuda.synchronize()
-    assert torch.equal(iou, iou_ref)
     n = 57
     al = torch.zeros((n, 1), device=cuda)
     C.boxes_aligned_overlap_bev_gpu(a[:n].contiguous(), b, al)
-    al_ref = torch.zeros_like(al)
-    ref.ref_boxes_aligned_overlap(n, _p(a[:n].contiguous()), _p(b), _p(al_ref))
-    torch.cuda.synchronize()
-    assert torch.equal(al, al_ref)
+    got = {"overlap": ov, "iou_bev": iou, "aligned_overlap": al}
+    for k, t in got.items():
+        w = torch.from_numpy(gold[k]).to(cuda)
+        assert torch.equal(t, w), f"{k}: max diff {(t - w).abs().max().item()} from the reference's recorded output"
+    ref = _ref_gpu()
+    if ref is not None:
+        for k, w in iou_reference(ref, a, b).items():
+            assert torch.equal(got[k], w), f"{k}: max diff {(got[k] - w).abs().max().item()}"
     # and within float tolerance of the CPU oracle (libm vs ocml trig)
     np.testing.assert_allclose(ov.cpu().numpy(), oracle.boxes_overlap_bev(A, Bx), rtol=1e-4, atol=1e-4)
     np.testing.assert_allclose(iou.cpu().numpy(), oracle.boxes_iou_bev(A, Bx), rtol=1e-4, atol=1e-5)
@@ -184,26 +214,46 @@ def _sweep(mask, n):
     return keep
 
 
-@pytest.mark.parametrize("n", [1, 60, 64, 65, 200, 700])
+NMS_THRESHOLDS = (0.1, 0.45, 1.0)
+NMS_SIZES = (1, 60, 64, 65, 200, 700)
+
+
+def nms_inputs(rng, n):
+    """boxes (n, 7) and scores (n,) of the NMS parity test"""
+    boxes = syn.random_boxes(rng, n, 6.0 if n < 300 else 14.0)
+    scores = rng.uniform(0, 1, n).astype(np.float32)
+    return boxes, scores
+
+
+def nms_reference_mask(ref, sb, thresh, rotated):
+    """the reference's NMS kernel's (n * ceil(n / 64),) u64 suppression mask over score-sorted device boxes sb"""
+    n = sb.shape[0]
+    mask = torch.zeros((n * ((n + 63) // 64),), dtype=torch.int64, device=sb.device)
+    (ref.ref_nms_mask if rotated else ref.ref_nms_normal_mask)(_p(sb), _p(mask), n, ctypes.c_float(thresh))
+    torch.cuda.synchronize()
+    return mask.cpu().numpy().astype(np.uint64)
+
+
+@pytest.mark.parametrize("n", NMS_SIZES)
 @pytest.mark.parametrize("rotated", [False, True])
 def test_nms_keep_lists_bit_exact(cuda, oracle, rng, n, rotated):
     from findnpropagate_amd.iou3d_nms import iou3d_nms_cuda as C, iou3d_nms_utils as U
 
     ref = _ref_gpu()
-    boxes = syn.random_boxes(rng, n, 6.0 if n < 300 else 14.0)
-    scores = rng.uniform(0, 1, n).astype(np.float32)
+    gold = _iou_gold()
+    boxes, scores = nms_inputs(rng, n)
     d_boxes, d_scores = torch.from_numpy(boxes).to(cuda), torch.from_numpy(scores).to(cuda)
     order = torch.sort(d_scores, descending=True)[1]
     sb = d_boxes[order].contiguous()
-    for thresh in (0.1, 0.45, 1.0):
+    tag = f"nms_{'rotated' if rotated else 'normal'}_{n}"
+    assert _sha(sb.cpu().numpy()) == str(gold[f"{tag}_inputs_sha256"]), "inputs differ from the recorded ones"
+    for thresh in NMS_THRESHOLDS:
         keep, num = C._nms_device(sb, thresh, rotated)
         got = keep[: int(num.item())].cpu().tolist()
-        cb = (n + 63) // 64
-        mask = torch.zeros((n * cb,), dtype=torch.int64, device=cuda)
-        (ref.ref_nms_mask if rotated else ref.ref_nms_normal_mask)(_p(sb), _p(mask), n, ctypes.c_float(thresh))
-        torch.cuda.synchronize()
-        m = mask.cpu().numpy().astype(np.uint64)
-        assert got == _sweep(m, n), "keep list differs from the reference kernel + reference sweep"
+        m = gold[f"{tag}_mask_{thresh}"]
+        assert got == _sweep(m, n), "keep list differs from the reference kernel's recorded mask + reference sweep"
+        if ref is not None:
+            assert np.array_equal(nms_reference_mask(ref, sb, thresh, rotated), m), "the reference kernel's mask differs from its recorded one"
         want = oracle.nms(sb.cpu().numpy(), thresh, rotated).tolist()
         assert got == want, "keep list differs from the CPU oracle"
         # pybind-shaped entry point: CPU int64 keep + count

@@ -4,7 +4,7 @@ points and ~150 k voxels per scene, nine times the single-sweep scenes of the ot
 41 x 1440 x 1440 grid: voxel rows bit-exact against the oracle's sequential voxeliser (with the `max_voxels` rule firing in
 the middle of a scene), site sets of every stage, the f32 engine equal to the oracle bit for bit, bf16 features against the
 bf16-emulating oracle.  The engine's heuristics (class-sorted sweep of stage 4, tile windows of stages 2-3) were sized on
-single-sweep geometry: the statistics they rest on are printed by bench.py's secondary.ten_sweep; here only results count."""
+single-sweep geometry: the statistics they rest on are printed by bench.py --full's secondary.ten_sweep; here only results count."""
 import numpy as np
 import pytest
 import torch

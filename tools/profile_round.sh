@@ -5,7 +5,7 @@ TAG=${1:-round}; B=${2:-128}; shift; shift; EXTRA="$@"   # extra bench.py args, 
 R=${GRAFT_REPO_ROOT:-$PWD}; O=$R/gpurun_out/$TAG
 mkdir -p $O/stats $O/fetch $O/write $O/sq
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --batch $B $EXTRA > $O/bench_b$B.json 2> $O/bench.err
+python3 $R/bench.py --full --batch $B $EXTRA > $O/bench_b$B.json 2> $O/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $O/stats -- python3 $R/bench.py --batch $B --cpu-scenes 0 --no-sweep --no-secondary $EXTRA > $O/bench_under_rocprof.json 2>/dev/null
 # the same step with every kernel a plain stream launch (no second branch: kernels do not overlap, so per-kernel averages are
 # comparable with the bench line's per_class, which comes from bracketed stream launches)
