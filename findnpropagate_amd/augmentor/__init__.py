@@ -1,3 +1,3 @@
-from . import pseudo_loader
+from . import data_augmentor, pseudo_loader
 
-__all__ = ["pseudo_loader"]
+__all__ = ["data_augmentor", "pseudo_loader"]

@@ -10,7 +10,7 @@ and every call is enqueued on ``torch.cuda.current_stream()``.
 import ctypes
 import os
 import re
-from ctypes import POINTER, c_char_p, c_float, c_int, c_int64, c_uint, c_void_p
+from ctypes import POINTER, c_char_p, c_double, c_float, c_int, c_int64, c_uint, c_uint64, c_void_p
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 # FNP_LIB_PATH: development override used by tools/ to A/B kernel builds; never set in production
@@ -20,6 +20,11 @@ HEADER_PATH = os.path.join(os.path.dirname(_HERE), "include", "fnp.h")
 FNP_F32 = 0
 FNP_BF16 = 1
 FNP_F16 = 2
+
+FNP_SHUFFLE_NONE = 0
+FNP_SHUFFLE_DEVICE = 1
+FNP_SHUFFLE_EXPLICIT = 2
+FNP_PREP_MAX_STEPS = 6
 
 _ERRORS = {-1: "FNP_ERR_ARG", -2: "FNP_ERR_LAUNCH", -3: "FNP_ERR_HIP", -4: "FNP_ERR_WORKSPACE"}
 
@@ -117,6 +122,9 @@ SIGNATURES = {
     "fnp_voxelize": (c_int, [P, c_int, P, POINTER(VoxelCfg), POINTER(RankGridC), P, c_int64,
                              P, P, P, P, P, P, c_int, P]),
     "fnp_host_voxelize": (c_int, [P, c_int, POINTER(VoxelCfg), P, P, P, c_int]),
+    "fnp_prepare_points_workspace_bytes": (c_int64, [c_int64]),
+    "fnp_prepare_points": (c_int, [P, c_int64, c_int, P, c_int, P, c_int, c_double, c_double, c_double, c_double,
+                                   c_int, P, c_int64, c_uint64, c_float, P, c_int64, P, P, P]),
     "fnp_rulebook_subm": (c_int, [P, P, c_int, POINTER(ConvGeom), POINTER(RankGridC), P, P]),
     "fnp_rulebook_strided": (c_int, [P, P, c_int, POINTER(ConvGeom), POINTER(RankGridC), POINTER(RankGridC),
                                      P, P, c_int, P, P, c_int64, P]),

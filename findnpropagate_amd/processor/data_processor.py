@@ -8,6 +8,12 @@ max_num_voxels).generate(points)` returns (voxels (M,P,C) f32, coordinates (M,3)
 num_points (M,) int32) with the reference's sequential first-come semantics.  Like the reference's it is a HOST
 generator (fnp_host_voxelize): DataProcessor creates it lazily inside DataLoader workers, where no GPU context may
 be created after a fork; pass device="cuda" for the device voxeliser (main process / spawn workers only).
+
+`DataProcessor(..., deferred=True)` (opt-in, default off) leaves the points half of mask_points_and_boxes_outside_range and
+shuffle_points to the device: the points are not touched here, data_dict['prep_mask'] / data_dict['prep_shuffle'] say that
+the step is due, and sparse.prepare_points runs it (with the augmentor's deferred program) in front of the device voxeliser.
+The boxes are masked here as before.  Deferred points cannot be voxelised on the host: such a queue takes
+transform_points_to_voxels_placeholder.
 """
 from functools import partial
 
@@ -64,8 +70,9 @@ def _cfg(config, key, default=None):
 class DataProcessor(object):
     """data_processor.py:64-78,405-420: the queue of bound processors, run in config order."""
 
-    def __init__(self, processor_configs, point_cloud_range, training, num_point_features):
+    def __init__(self, processor_configs, point_cloud_range, training, num_point_features, deferred=False):
         self.point_cloud_range = np.asarray(point_cloud_range)
+        self.deferred = bool(deferred)
         self.training = training
         self.num_point_features = num_point_features
         self.mode = 'train' if training else 'test'
@@ -76,12 +83,17 @@ class DataProcessor(object):
             name = _cfg(cur_cfg, 'NAME')
             if not hasattr(self, name):
                 raise NotImplementedError(f"DataProcessor.{name} is not on the hot path of this build")
+            if self.deferred and name == 'transform_points_to_voxels':
+                raise ValueError("DataProcessor(deferred=True) leaves the points unmasked: voxelise them on the device "
+                                 "(transform_points_to_voxels_placeholder + sparse.prepare_points)")
             self.data_processor_queue.append(getattr(self, name)(config=cur_cfg))
 
     def mask_points_and_boxes_outside_range(self, data_dict=None, config=None):
         if data_dict is None:
             return partial(self.mask_points_and_boxes_outside_range, config=config)
-        if data_dict.get('points', None) is not None:
+        if self.deferred:
+            data_dict['prep_mask'] = True
+        elif data_dict.get('points', None) is not None:
             mask = mask_points_by_range(data_dict['points'], self.point_cloud_range)
             data_dict['points'] = data_dict['points'][mask]
         if data_dict.get('gt_boxes', None) is not None and _cfg(config, 'REMOVE_OUTSIDE_BOXES') and self.training:
@@ -94,7 +106,9 @@ class DataProcessor(object):
     def shuffle_points(self, data_dict=None, config=None):
         if data_dict is None:
             return partial(self.shuffle_points, config=config)
-        if _cfg(config, 'SHUFFLE_ENABLED')[self.mode]:
+        if _cfg(config, 'SHUFFLE_ENABLED')[self.mode] and self.deferred:
+            data_dict['prep_shuffle'] = True
+        elif _cfg(config, 'SHUFFLE_ENABLED')[self.mode]:
             points = data_dict['points']
             data_dict['points'] = points[np.random.permutation(points.shape[0])]
         return data_dict

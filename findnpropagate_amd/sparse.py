@@ -195,6 +195,65 @@ def stage_points(points, batch_offsets, dst_points, dst_offsets, n_prev, pad):
                                 _l.ptr(batch_offsets), batch_offsets.numel(), _l.ptr(dst_offsets), _l.stream()), "fnp_stage_points")
 
 
+PREP_PAD = 1.0e9   # rows behind the kept points of prepare_points: outside every range, dropped by the voxeliser
+
+
+def prepare_points(points, batch_offsets, batch_size, program, point_cloud_range, shuffle=None, seed=0, out=None):
+    """World augmentation + range mask + point shuffle of a batch on the device, in front of voxelize (fnp_prepare_points).
+
+    points (N,C) f32 device, scenes concatenated; batch_offsets (B+1,) int32 device.
+    program: (B,K,4) f32 device, K <= 6 (augmentor.data_augmentor.stack_programs of the per-scene programs DataAugmentor records
+    in deferred mode), or None for no augmentation.  point_cloud_range: the 6 numbers of POINT_CLOUD_RANGE (x and y are tested,
+    both ends inclusive, as mask_points_by_range does).
+    shuffle: None (kept rows in order), "device" (a keyed permutation per scene, reproducible for a seed; not numpy's), or a (K,)
+    int32 device tensor: scene b's slice [o_b, o_b + m_b) holds the numpy permutation of its m_b kept rows (the reference's order).
+    out: a dict returned by an earlier call with the same N, C and B, whose buffers are reused (a captured graph's static outputs).
+
+    Returns dict(points (N,C) f32: the kept rows scene after scene, then PREP_PAD rows; batch_offsets (B+1,) int32: the new
+    offsets; n (1,) int32: the kept count; batch_size) — points and batch_offsets are what voxelize / forward_points take, over
+    all N rows.  No host sync, fixed shapes: capturable."""
+    L = _l.load()
+    _l.require_device(points, batch_offsets, program)
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.is_contiguous()
+    assert batch_offsets.dtype == torch.int32 and batch_offsets.numel() == batch_size + 1 and batch_offsets.is_contiguous()
+    n, C = points.shape
+    dev = points.device
+    K = 0
+    if program is not None:
+        assert program.dtype == torch.float32 and program.dim() == 3 and program.shape[0] == batch_size and program.shape[2] == 4
+        assert program.is_contiguous() and program.shape[1] <= _l.FNP_PREP_MAX_STEPS
+        K = int(program.shape[1])
+    perm = None
+    if shuffle is None:
+        mode = _l.FNP_SHUFFLE_NONE
+    elif isinstance(shuffle, str):
+        if shuffle != "device":
+            raise ValueError(f"shuffle={shuffle!r}: None, 'device' or a permutation tensor")
+        mode = _l.FNP_SHUFFLE_DEVICE
+    else:
+        perm = shuffle
+        _l.require_device(perm)
+        assert perm.dtype == torch.int32 and perm.dim() == 1 and perm.is_contiguous()
+        mode = _l.FNP_SHUFFLE_EXPLICIT
+    rng = [float(v) for v in point_cloud_range]
+    ws_bytes = int(L.fnp_prepare_points_workspace_bytes(n))
+    _l.check(min(ws_bytes, 0), "fnp_prepare_points_workspace_bytes")
+    if out is None:
+        out = dict(points=torch.empty((n, C), dtype=torch.float32, device=dev),
+                   workspace=torch.empty((ws_bytes,), dtype=torch.uint8, device=dev))
+        off = torch.empty((batch_size + 1,), dtype=torch.int32, device=dev)
+        out.update(batch_offsets=off, n=off[batch_size:], batch_size=batch_size)
+    else:
+        assert out["points"].shape == (n, C) and out["batch_offsets"].numel() == batch_size + 1 and out["workspace"].numel() >= ws_bytes
+    rc = L.fnp_prepare_points(_l.ptr(points) if n else None, n, C, _l.ptr(batch_offsets), batch_size,
+                              _l.ptr(program) if K else None, K, rng[0], rng[1], rng[3], rng[4],
+                              mode, _l.ptr(perm) if perm is not None and perm.numel() else None, 0 if perm is None else perm.numel(),
+                              int(seed) & 0xFFFFFFFFFFFFFFFF, PREP_PAD, _l.ptr(out["workspace"]), out["workspace"].numel(),
+                              _l.ptr(out["points"]) if n else None, _l.ptr(out["batch_offsets"]), _l.stream())
+    _l.check(rc, "fnp_prepare_points")
+    return out
+
+
 def voxelize(points, batch_offsets, batch_size, cfg, grid=None, want_voxels=False, workspace=None):
     """points (N,C) f32 device, batch_offsets (B+1,) int32 device.
 

@@ -225,6 +225,35 @@ int fnp_host_voxelize(const float *points, int n_points, const fnp_voxel_cfg *cf
                       int *num_points, int max_rows);
 
 /* ------------------------------------------------------------------------------------------
+ * Point preparation in front of fnp_voxelize — replaces, on the device, the world augmentations of DataAugmentor
+ * (pcdet/datasets/augmentor/data_augmentor.py:59-181: random_world_flip / _rotation / _scaling / _translation),
+ * the points half of mask_points_and_boxes_outside_range (data_processor.py:80-94, common_utils.py:78-81) and
+ * shuffle_points (data_processor.py:96-106), which the reference runs in numpy inside DataLoader workers.
+ * ------------------------------------------------------------------------------------------ */
+enum { FNP_SHUFFLE_NONE = 0, FNP_SHUFFLE_DEVICE = 1, FNP_SHUFFLE_EXPLICIT = 2 };
+enum { FNP_PREP_MAX_STEPS = 6 };
+
+int64_t fnp_prepare_points_workspace_bytes(int64_t n_points);
+
+/* points (N, C) f32, scenes concatenated, batch_offsets (B+1,) int32 (scene b owns rows [off[b], off[b+1])).
+ * program (B, K, 4) f32, K <= FNP_PREP_MAX_STEPS (nullable when K = 0): scene b's ops in the order the config lists them,
+ *   one row {op, a, b, c} per step: 0 none, 1 flip x (y = -y), 2 flip y (x = -x), 3 rotate about z (a = cos, b = sin of the
+ *   f32 angle, computed on the host), 4 scale xyz by a, 5 translate xyz by (a, b, c).  f32 arithmetic of the reference.
+ * The range (host values): a point is kept iff x_min <= x <= x_max and y_min <= y <= y_max after its program (in f64, as numpy
+ *   compares an f32 array with the f64 range); z is not tested.
+ * shuffle_mode: FNP_SHUFFLE_NONE keeps the kept rows in order; FNP_SHUFFLE_DEVICE places the k-th kept row of scene b at a
+ *   keyed bijection of k in [0, m_b) (seed and b are the key: reproducible, independent of the rest of the batch);
+ *   FNP_SHUFFLE_EXPLICIT writes out[j] = kept[perm[j]] with perm (n_perm,) int32 device, perm[o_b + j] in [0, m_b) the scene's
+ *   own permutation of its kept rows (numpy's np.random.permutation order after the mask).
+ * Outputs: out_points (N, C) f32: the kept rows, scene after scene, then rows [kept, N) = pad in every column (pad must lie
+ *   outside every range: fnp_voxelize over all N rows drops them); out_offsets (B+1,) int32: the new scene offsets, and
+ *   out_offsets[B] the total kept count.  Everything stays on the device; no host synchronisation. */
+int fnp_prepare_points(const float *points, int64_t n_points, int num_features, const int *batch_offsets, int batch_size,
+                       const float *program, int program_steps, double x_min, double y_min, double x_max, double y_max,
+                       int shuffle_mode, const int *perm, int64_t n_perm, uint64_t seed, float pad,
+                       void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Rulebooks — replace spconv's indice-pair generation for SubMConv3d / SparseConv3d
  * (call sites pcdet/models/backbones_3d/spconv_backbone.py:12-17,39-46,193-234).
  * Output-stationary layout: nbr[k*cap + o] = input row feeding output row o through kernel

@@ -1,0 +1,122 @@
+#!/usr/bin/env python3
+"""Point preparation (world augmentation + range mask + shuffle) on the device against the host: one JSON line.
+
+device: sparse.prepare_points (fnp_prepare_points, device shuffle and explicit-permutation modes), median of HIP-event timed
+        launches, for B = 4 ten-sweep scenes (~300 k points each) and B = 128 single-sweep scenes (~30 k points each);
+host:   the same work as the reference does it per scene in DataLoader workers (DataAugmentor host mode + mask_points_by_range +
+        np.random.permutation), wall time per batch with 1 worker process and with 16, torch at one thread per process.
+Host timings run first, in forked workers, before this process touches the GPU.
+
+    python tools/bench_prepare.py [--reps 50]
+"""
+import argparse
+import json
+import multiprocessing as mp
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+from findnpropagate_amd import synthetic as syn  # noqa: E402
+
+CFG = [dict(NAME='random_world_flip', ALONG_AXIS_LIST=['x', 'y']),
+       dict(NAME='random_world_rotation', WORLD_ROT_ANGLE=[-0.78539816, 0.78539816]),
+       dict(NAME='random_world_scaling', WORLD_SCALE_RANGE=[0.9, 1.1]),
+       dict(NAME='random_world_translation', NOISE_TRANSLATE_STD=[0.5, 0.5, 0.5])]
+_SCENES = None
+
+
+def _init_worker():
+    import torch
+
+    import findnpropagate_amd.augmentor.data_augmentor  # noqa: F401
+    import findnpropagate_amd.processor.data_processor  # noqa: F401
+
+    torch.set_num_threads(1)
+
+
+def _host_scene(args):
+    from findnpropagate_amd.augmentor.data_augmentor import DataAugmentor
+    from findnpropagate_amd.processor.data_processor import mask_points_by_range
+
+    b, seed = args
+    np.random.seed(seed)
+    d = DataAugmentor(None, CFG, []).forward(dict(points=_SCENES[b].copy(), gt_boxes=np.zeros((0, 9), np.float32)))
+    p = d['points']
+    p = p[mask_points_by_range(p, np.array(syn.POINT_CLOUD_RANGE, np.float32))]
+    return int(p[np.random.permutation(p.shape[0])].shape[0])
+
+
+def host_time(scenes, workers, reps=3):
+    global _SCENES
+    _SCENES = scenes
+    best = float("inf")
+    with mp.get_context("fork").Pool(workers, initializer=_init_worker) as pool:
+        pool.map(_host_scene, [(b % len(scenes), b) for b in range(2 * workers)], chunksize=1)      # (first touch)
+        for r in range(reps):
+            t = time.perf_counter()
+            pool.map(_host_scene, [(b, 100 * r + b) for b in range(len(scenes))], chunksize=1)
+            best = min(best, time.perf_counter() - t)
+    return best * 1e3
+
+
+def device_time(scenes, reps):
+    import torch
+
+    from findnpropagate_amd import sparse as S
+    from findnpropagate_amd.augmentor.data_augmentor import DataAugmentor, stack_programs, PROGRAM_KEY
+
+    dev = torch.device("cuda", 0)
+    progs = []
+    for b, s in enumerate(scenes):
+        np.random.seed(b)
+        progs.append(DataAugmentor(None, CFG, [], deferred=True).forward(dict(points=s, gt_boxes=np.zeros((0, 9), np.float32)))[PROGRAM_KEY])
+    pts = torch.from_numpy(np.concatenate(scenes)).to(dev)
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum([s.shape[0] for s in scenes])]).astype(np.int32)).to(dev)
+    prog = torch.from_numpy(stack_programs(progs)).to(dev)
+    B = len(scenes)
+    out = S.prepare_points(pts, off, B, prog, syn.POINT_CLOUD_RANGE, shuffle="device")
+    kept = int(out["n"].item())
+    perm = torch.cat([torch.randperm(int(m), device=dev, dtype=torch.int64).to(torch.int32)
+                      for m in (out["batch_offsets"][1:] - out["batch_offsets"][:-1]).tolist()])
+    res = {}
+    for name, shuffle in (("device_shuffle", "device"), ("explicit_perm", perm), ("no_shuffle", None)):
+        for _ in range(5):
+            S.prepare_points(pts, off, B, prog, syn.POINT_CLOUD_RANGE, shuffle=shuffle, out=out)
+        ts = []
+        for _ in range(reps):
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            S.prepare_points(pts, off, B, prog, syn.POINT_CLOUD_RANGE, shuffle=shuffle, out=out)
+            z.record()
+            z.synchronize()
+            ts.append(a.elapsed_time(z) * 1e3)
+        res[name + "_us"] = round(float(np.median(ts)), 1)
+    res.update(points=int(pts.shape[0]), kept=kept, scenes=B)
+    return res
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=50)
+    ap.add_argument("--workers", type=int, default=16)
+    a = ap.parse_args()
+    pts, off = syn.make_sweeps_batch([0, 1, 2, 3])
+    sweeps = [pts[off[b]:off[b + 1]] for b in range(4)]
+    pts, off = syn.make_batch(range(128))
+    single = [pts[off[b]:off[b + 1]] for b in range(128)]
+    out = {"metric": "prepare_points"}
+    for name, scenes in (("b4_x_300k", sweeps), ("b128_x_30k", single)):
+        out[name] = {"host_1_worker_ms": round(host_time(scenes, 1), 2),
+                     f"host_{a.workers}_workers_ms": round(host_time(scenes, a.workers), 2)}
+    for name, scenes in (("b4_x_300k", sweeps), ("b128_x_30k", single)):
+        out[name].update(device_time(scenes, a.reps))
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
