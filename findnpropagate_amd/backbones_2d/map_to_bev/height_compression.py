@@ -6,7 +6,13 @@ Same constructor, attributes (`num_bev_features`) and batch_dict keys.  The dens
 module keeps the index map and, with `REUSE_OUTPUT: True` in the model cfg (our addition, default off: the
 reference returns a fresh tensor per call), also the output buffer.  `spatial_features` has the dtype of the encoded
 tensor's features — float32 by default (VoxelResBackBone8x FNP_OUT_DTYPE, the reference contract); OUT_DTYPE in this
-module's cfg ('fp32' | 'bf16' | 'fp16') overrides it (the features are cast before the one densifying pass)."""
+module's cfg ('fp32' | 'bf16' | 'fp16') overrides it (the features are cast before the one densifying pass).
+
+Training: when the encoded features require grad (and grad mode is on) the densification is differentiable
+(sparse.DenseFunction, backward fnp_sparse_to_dense_backward), as the reference's torch index assignment is, so the
+detector's loss reaches the 3D backbone; the OUT_DTYPE cast is a torch op on the graph.  Such an output is never the
+reused buffer."""
+import torch
 import torch.nn as nn
 
 from ... import sparse as S
@@ -19,7 +25,6 @@ class HeightCompression(nn.Module):
         self.num_bev_features = _get(model_cfg, "NUM_BEV_FEATURES")
         self.reuse_output = bool(_get(model_cfg, "REUSE_OUTPUT", False))
         od = _get(model_cfg, "OUT_DTYPE", "keep")
-        import torch
         self.out_dtype = {"keep": None, "fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[str(od).lower()]
         self._ws = None
         self._out = None
@@ -31,14 +36,18 @@ class HeightCompression(nn.Module):
             feats = feats.to(self.out_dtype)
         need = int(S._l.load().fnp_sparse_to_dense_workspace_bytes(t.batch_size, *t.spatial_shape))
         if self._ws is None or self._ws.numel() < need or self._ws.device != feats.device:
-            import torch
             self._ws = torch.empty((need,), dtype=torch.uint8, device=feats.device)
+        # an output that joins an autograd graph is a fresh tensor on every call: a consumer such as BaseBEVBackbone's first
+        # Conv2d keeps its input for the weight gradient, and the next forward's kernel would overwrite a reused buffer behind
+        # torch's version counter
+        grad = torch.is_grad_enabled() and feats.requires_grad
+        reuse = self.reuse_output and not grad
         out = None
-        if self.reuse_output and self._out is not None and self._out.dtype == feats.dtype and \
+        if reuse and self._out is not None and self._out.dtype == feats.dtype and \
                 tuple(self._out.shape) == (t.batch_size, feats.shape[1], *t.spatial_shape) and self._out.device == feats.device:
             out = self._out
         dense = S.to_dense(feats, t.indices, t.n_dev(), t.batch_size, list(t.spatial_shape), workspace=self._ws, out=out)
-        if self.reuse_output:
+        if reuse:
             self._out = dense
         N, C, D, H, W = dense.shape
         batch_dict["spatial_features"] = dense.view(N, C * D, H, W)

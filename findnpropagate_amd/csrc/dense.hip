@@ -214,6 +214,194 @@ int run_dense(const void *feats, const int *coords, const int *n_rows, int cap, 
     return launch_dense_write<T, 1>(feats, index, C, B, D, plane, out, fill, s);
 }
 
+// ---------------------------------------------------------------------------------------------------------------------
+// The adjoint of the writer (training through HeightCompression): grad_feats[r, :] = grad_out[b, :, z, y, x] for every
+// row r < n whose (b, z, y, x) lies in the grid, a plain copy; every other row gets 0 (the forward wrote nothing for it).
+// Same tiling as dense_write_kernel, read instead of written: one workgroup per 64*VEC consecutive cells of a (b,z) plane;
+// a tile without rows reads nothing; otherwise the lanes that own an occupied cell read their VEC cells of every channel
+// plane (coalesced, VEC*sizeof(T) bytes per lane) and park the occupied ones in padded LDS slots, then the workgroup writes
+// each staged row whole (C*sizeof(T) contiguous bytes, 16-byte stores where the row size and buffer allow).  A tile with
+// more than kSlots rows is done in passes of kSlots slots (each pass re-reads only the lanes whose cells it stages).
+
+// rows r < n: cell -> row in `index` (in the grid) or a zero row (outside); rows n .. cap-1: zero.  After this launch the
+// tile kernel writes exactly the rows the index map names, so every row of grad_feats is written once.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dense_grad_index_kernel(const int *__restrict__ coords, const int *__restrict__ n_rows,
+                                                                    int cap, int C, int B, int D, int H, int W, int *__restrict__ index,
+                                                                    T *__restrict__ grad_feats) {
+    const int n = min(*n_rows, cap);
+    for (int r = blockIdx.x * kThreads + threadIdx.x; r < n; r += gridDim.x * kThreads) {
+        const int4 c = reinterpret_cast<const int4 *>(coords)[r];
+        if (c.x < 0 || c.x >= B || c.y < 0 || c.y >= D || c.z < 0 || c.z >= H || c.w < 0 || c.w >= W) {
+            for (int e = 0; e < C; ++e) grad_feats[(long long)r * C + e] = (T)0;
+            continue;
+        }
+        index[(((long long)c.x * D + c.y) * H + c.z) * W + c.w] = r;
+    }
+    const long long end = (long long)cap * C;
+    for (long long t = (long long)n * C + (long long)blockIdx.x * kThreads + threadIdx.x; t < end; t += (long long)gridDim.x * kThreads)
+        grad_feats[t] = (T)0;
+}
+
+template <typename T, int VEC>
+__global__ __launch_bounds__(kThreads) void dense_grad_kernel(const T *__restrict__ grad_out, const int *__restrict__ index, int C,
+                                                              int D, long long plane, int tiles_per_plane, int quad,
+                                                              T *__restrict__ grad_feats) {
+    extern __shared__ __attribute__((aligned(16))) unsigned char fnp_dense_smem[];
+    typedef int IVec __attribute__((ext_vector_type(VEC)));
+    typedef T TVec __attribute__((ext_vector_type(VEC)));
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const long long tile = blockIdx.x;
+    const long long bz = tile / tiles_per_plane;
+    const long long l0 = (tile % tiles_per_plane) * (64 * VEC);
+    const int b = (int)(bz / D), z = (int)(bz % D);
+    const bool in = l0 + (long long)VEC * lane < plane;
+    int r[VEC];
+    if (in) {
+        if constexpr (VEC == 1) {
+            r[0] = index[bz * plane + l0 + lane];
+        } else {
+            const IVec v = *reinterpret_cast<const IVec *>(index + bz * plane + l0 + (long long)VEC * lane);
+#pragma unroll
+            for (int j = 0; j < VEC; ++j) r[j] = v[j];
+        }
+    } else {
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) r[j] = -1;
+    }
+    const unsigned long long below = (1ull << lane) - 1ull;
+    int total = 0, slot[VEC];                                    // slot of cell j (when occupied): rank among the tile's rows
+#pragma unroll
+    for (int j = 0; j < VEC; ++j) {
+        const unsigned long long occ = __ballot(r[j] >= 0);    // (same in all four waves: they own the same cells)
+        slot[j] = total + __popcll(occ & below);
+        total += __popcll(occ);
+    }
+    if (total == 0) return;                                      // (workgroup-uniform)
+
+    const int row_bytes = C * (int)sizeof(T), stride = row_bytes + 4;
+    int *slot_row = reinterpret_cast<int *>(fnp_dense_smem + kSlots * stride);
+    const T *g = grad_out + ((long long)b * C * D + z) * plane + l0 + (long long)VEC * lane;   // channel c adds c * D * plane
+    const long long cstep = (long long)D * plane;
+    constexpr int U = 8;                                         // channel planes in flight per wave
+    for (int p0 = 0; p0 < total; p0 += kSlots) {                 // one pass unless the tile holds more than kSlots rows
+        bool mine[VEC], any = false;
+#pragma unroll
+        for (int j = 0; j < VEC; ++j) {
+            mine[j] = r[j] >= 0 && slot[j] >= p0 && slot[j] < p0 + kSlots;
+            any |= mine[j];
+            if (mine[j] && wave == 0) slot_row[slot[j] - p0] = r[j];
+        }
+        if (any) {
+            for (int c0 = wave; c0 < C; c0 += 4 * U) {
+                TVec v[U];
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (c0 + 4 * u < C) {
+                        if constexpr (VEC == 1) v[u][0] = g[(c0 + 4 * u) * cstep];
+                        else v[u] = *reinterpret_cast<const TVec *>(g + (c0 + 4 * u) * cstep);
+                    }
+#pragma unroll
+                for (int u = 0; u < U; ++u)
+                    if (c0 + 4 * u < C) {
+#pragma unroll
+                        for (int j = 0; j < VEC; ++j)
+                            if (mine[j]) reinterpret_cast<T *>(fnp_dense_smem + (slot[j] - p0) * stride)[c0 + 4 * u] = v[u][j];
+                    }
+            }
+        }
+        __syncthreads();
+        const int cnt = min(total - p0, kSlots);
+        unsigned char *dst0 = reinterpret_cast<unsigned char *>(grad_feats);
+        if (quad) {   // row_bytes % 16 == 0, grad_feats 16-byte aligned
+            const int qpr = row_bytes >> 4;
+            for (int i = threadIdx.x; i < cnt * qpr; i += kThreads) {
+                const int k = i / qpr, q = i - k * qpr;
+                const unsigned *src = reinterpret_cast<const unsigned *>(fnp_dense_smem + k * stride) + 4 * q;
+                const uint4 v = make_uint4(src[0], src[1], src[2], src[3]);
+                *reinterpret_cast<uint4 *>(dst0 + (size_t)slot_row[k] * row_bytes + 16 * q) = v;
+            }
+        } else {
+            const int wpr = row_bytes >> 2;
+            for (int i = threadIdx.x; i < cnt * wpr; i += kThreads) {
+                const int k = i / wpr, q = i - k * wpr;
+                reinterpret_cast<unsigned *>(dst0 + (size_t)slot_row[k] * row_bytes)[q] =
+                    reinterpret_cast<const unsigned *>(fnp_dense_smem + k * stride)[q];
+            }
+        }
+        __syncthreads();                                         // (before the next pass overwrites the slots)
+    }
+}
+
+// Rows without a workspace, or whose size the tile kernel does not take: one thread per element of grad_feats.
+template <typename T>
+__global__ __launch_bounds__(kThreads) void dense_grad_rows_kernel(const T *__restrict__ grad_out, const int *__restrict__ coords,
+                                                                   const int *__restrict__ n_rows, int cap, int C, int B, int D, int H,
+                                                                   int W, T *__restrict__ grad_feats) {
+    const int n = min(*n_rows, cap);
+    const long long total = (long long)cap * C;
+    const long long vol = (long long)D * H * W;
+    for (long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x; t < total; t += (long long)gridDim.x * blockDim.x) {
+        const int row = (int)(t / C), c = (int)(t % C);
+        T v = (T)0;
+        if (row < n) {
+            const int4 cd = reinterpret_cast<const int4 *>(coords)[row];
+            if (cd.x >= 0 && cd.x < B && cd.y >= 0 && cd.y < D && cd.z >= 0 && cd.z < H && cd.w >= 0 && cd.w < W)
+                v = grad_out[((long long)cd.x * C + c) * vol + ((long long)cd.y * H + cd.z) * W + cd.w];
+        }
+        grad_feats[t] = v;
+    }
+}
+
+template <typename T, int VEC>
+int launch_dense_grad(const void *grad_out, const int *index, int C, int B, int D, long long plane, void *grad_feats, hipStream_t s) {
+    const int row_bytes = C * (int)sizeof(T);
+    const int tiles_per_plane = (int)((plane + 64 * VEC - 1) / (64 * VEC));
+    const long long tiles = (long long)B * D * tiles_per_plane;
+    if (tiles > 0x7fffffffll) return FNP_ERR_ARG;
+    const int quad = row_bytes % 16 == 0 && (uintptr_t)grad_feats % 16 == 0;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(dense_grad_kernel<T, VEC>), dim3((unsigned)tiles), dim3(kThreads),
+                       kSlots * (row_bytes + 4) + kSlots * 4, s, (const T *)grad_out, index, C, D, plane, tiles_per_plane, quad,
+                       (T *)grad_feats);
+    FNP_LAUNCH_CHECK();
+    return FNP_OK;
+}
+
+template <typename T>
+int run_dense_backward(const void *grad_out, const int *coords, const int *n_rows, int cap, int C, int B, int D, int H, int W,
+                       void *grad_feats, void *ws, int64_t ws_bytes, hipStream_t s) {
+    const long long plane = (long long)H * W, cells = (long long)B * D * plane;
+    const int row_bytes = C * (int)sizeof(T);
+    const bool tiled = ws != nullptr && row_bytes % 4 == 0 && kSlots * (row_bytes + 4) + kSlots * 4 <= 64 * 1024;
+    if (!tiled) {
+        hipLaunchKernelGGL(HIP_KERNEL_NAME(dense_grad_rows_kernel<T>), dim3(fnp_grid_for((long long)cap * C, kThreads, 256 * 16)),
+                           dim3(kThreads), 0, s, (const T *)grad_out, coords, n_rows, cap, C, B, D, H, W, (T *)grad_feats);
+        FNP_LAUNCH_CHECK();
+        return FNP_OK;
+    }
+    if (ws_bytes < cells * 4) return FNP_ERR_WORKSPACE;
+    int *index = (int *)ws;
+    {
+        const int frc = fnp_fill_words(index, cells, 0xffffffffu, s);
+        if (frc) return frc;
+    }
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(dense_grad_index_kernel<T>), dim3(fnp_grid_for(cap, kThreads)), dim3(kThreads), 0, s, coords,
+                       n_rows, cap, C, B, D, H, W, index, (T *)grad_feats);
+    FNP_LAUNCH_CHECK();
+    const bool al = ((uintptr_t)grad_out % 16 == 0) && ((uintptr_t)ws % 16 == 0);
+    constexpr int kMaxVec = 16 / (int)sizeof(T) < FNP_DENSE_VEC ? 16 / (int)sizeof(T) : FNP_DENSE_VEC;
+    if constexpr (kMaxVec >= 8) {
+        if (al && plane % 8 == 0) return launch_dense_grad<T, 8>(grad_out, index, C, B, D, plane, grad_feats, s);
+    }
+    if constexpr (kMaxVec >= 4) {
+        if (al && plane % 4 == 0) return launch_dense_grad<T, 4>(grad_out, index, C, B, D, plane, grad_feats, s);
+    }
+    if constexpr (kMaxVec >= 2) {
+        if (al && plane % 2 == 0) return launch_dense_grad<T, 2>(grad_out, index, C, B, D, plane, grad_feats, s);
+    }
+    return launch_dense_grad<T, 1>(grad_out, index, C, B, D, plane, grad_feats, s);
+}
+
 }  // namespace
 
 extern "C" int64_t fnp_sparse_to_dense_workspace_bytes(int B, int D, int H, int W) {
@@ -230,6 +418,8 @@ extern "C" int fnp_sparse_to_dense(const void *feats, int dtype, const int *coor
         return run_dense<float>(feats, coords, n_rows, cap, C, B, D, H, W, out, workspace, workspace_bytes, (hipStream_t)stream);
     if (dtype == FNP_BF16)
         return run_dense<__bf16>(feats, coords, n_rows, cap, C, B, D, H, W, out, workspace, workspace_bytes, (hipStream_t)stream);
+    if (dtype == FNP_F16)
+        return run_dense<_Float16>(feats, coords, n_rows, cap, C, B, D, H, W, out, workspace, workspace_bytes, (hipStream_t)stream);
     return FNP_ERR_ARG;
 }
 
@@ -244,5 +434,27 @@ extern "C" int fnp_sparse_to_dense_fill(const void *feats, int dtype, const int 
         return run_dense<float>(feats, coords, n_rows, cap, C, B, D, H, W, out, workspace, workspace_bytes, (hipStream_t)stream, fill);
     if (dtype == FNP_BF16)
         return run_dense<__bf16>(feats, coords, n_rows, cap, C, B, D, H, W, out, workspace, workspace_bytes, (hipStream_t)stream, fill);
+    if (dtype == FNP_F16)
+        return run_dense<_Float16>(feats, coords, n_rows, cap, C, B, D, H, W, out, workspace, workspace_bytes, (hipStream_t)stream, fill);
+    return FNP_ERR_ARG;
+}
+
+// The adjoint of fnp_sparse_to_dense (backward of HeightCompression's densification): grad_out (B,C,D,H,W) -> grad_feats
+// (cap, C), same dtype.  Every row is written: rows r < n in the grid get a copy of their cell's C values, the rest 0.
+// With a workspace (the cell -> row map, rebuilt here) the plane-tiled gather runs; without one, a row-driven gather.
+extern "C" int fnp_sparse_to_dense_backward(const void *grad_out, int dtype, const int *coords, const int *n_rows, int cap, int C,
+                                            int B, int D, int H, int W, void *grad_feats, void *workspace, int64_t workspace_bytes,
+                                            fnp_stream_t stream) {
+    if (!grad_out || !coords || !n_rows || !grad_feats || cap <= 0 || C <= 0 || B <= 0 || D <= 0 || H <= 0 || W <= 0)
+        return FNP_ERR_ARG;
+    if (dtype == FNP_F32)
+        return run_dense_backward<float>(grad_out, coords, n_rows, cap, C, B, D, H, W, grad_feats, workspace, workspace_bytes,
+                                         (hipStream_t)stream);
+    if (dtype == FNP_BF16)
+        return run_dense_backward<__bf16>(grad_out, coords, n_rows, cap, C, B, D, H, W, grad_feats, workspace, workspace_bytes,
+                                          (hipStream_t)stream);
+    if (dtype == FNP_F16)
+        return run_dense_backward<_Float16>(grad_out, coords, n_rows, cap, C, B, D, H, W, grad_feats, workspace, workspace_bytes,
+                                            (hipStream_t)stream);
     return FNP_ERR_ARG;
 }

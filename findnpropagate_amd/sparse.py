@@ -930,7 +930,55 @@ def conv_wgrad(feat_in, grad_out, rb, n_out_dev, Cin, Cout, pairs=None, module_s
 def to_dense(features, indices, n_dev, batch_size, shape, workspace=None, out=None, fill=None):
     """SparseConvTensor.dense(): (B, C, D, H, W), written once (zeros included) through a cell -> row map.
     workspace / out: optional persistent buffers of a caller that densifies every step.
-    fill: optional (C,) f32 device tensor — the value of cells without a row, per channel, instead of 0."""
+    fill: optional (C,) f32 device tensor — the value of cells without a row, per channel, instead of 0.
+    Differentiable in `features` when grad mode is on, features.requires_grad and fill is None (DenseFunction): the result is
+    then a fresh tensor (`out` is not used) and the backward is fnp_sparse_to_dense_backward."""
+    if fill is None and torch.is_grad_enabled() and features.requires_grad:
+        return DenseFunction.apply(features, indices, n_dev, batch_size, tuple(int(s) for s in shape), workspace)
+    return _to_dense(features, indices, n_dev, batch_size, shape, workspace, out, fill)
+
+
+class DenseFunction(torch.autograd.Function):
+    """to_dense with its adjoint: grad_features[r] = grad_out[b, :, z, y, x] for rows r < n in the grid, 0 elsewhere (what the
+    reference's spconv gets from torch autograd of its index assignment `out[b, :, z, y, x] = features`).  The backward rebuilds
+    the cell -> row map in a workspace of its own: a caller's workspace (HeightCompression._ws) is rewritten by that caller's
+    next forward, which may run before this backward (gradient accumulation, an eval-mode call)."""
+
+    @staticmethod
+    def forward(ctx, features, indices, n_dev, batch_size, shape, workspace):
+        ctx.save_for_backward(indices, n_dev)
+        ctx.geom = (batch_size, shape, features.shape[0])
+        return _to_dense(features, indices, n_dev, batch_size, shape, workspace, None, None)
+
+    @staticmethod
+    def backward(ctx, grad_out):
+        indices, n_dev = ctx.saved_tensors
+        B, shape, rows = ctx.geom
+        return dense_backward(grad_out, indices, n_dev, B, shape, cap=rows), None, None, None, None, None
+
+
+def dense_backward(grad_out, indices, n_dev, batch_size, shape, cap=None, workspace=None):
+    """The adjoint of to_dense (fnp_sparse_to_dense_backward): grad_out (B, C, D, H, W) -> (cap, C) of its dtype; row r < n in the
+    grid gets its cell's C values, every other row 0.  cap: rows of the result (default: the rows of `indices`)."""
+    L = _l.load()
+    g = grad_out.contiguous()
+    B, C = int(batch_size), g.shape[1]
+    assert tuple(g.shape) == (B, C, *shape), (tuple(g.shape), B, shape)
+    cap = indices.shape[0] if cap is None else int(cap)
+    assert cap <= indices.shape[0]
+    gf = torch.empty((cap, C), dtype=g.dtype, device=g.device)
+    if cap == 0:
+        return gf
+    need = int(L.fnp_sparse_to_dense_workspace_bytes(B, *shape))
+    if workspace is None or workspace.numel() < need:
+        workspace = torch.empty((need,), dtype=torch.uint8, device=g.device)
+    rc = L.fnp_sparse_to_dense_backward(_l.ptr(g), _l.dtype_code(g), _l.ptr(indices), _l.ptr(n_dev), cap, C, B, *shape, _l.ptr(gf),
+                                        _l.ptr(workspace), workspace.numel(), _l.stream())
+    _l.check(rc, "fnp_sparse_to_dense_backward")
+    return gf
+
+
+def _to_dense(features, indices, n_dev, batch_size, shape, workspace=None, out=None, fill=None):
     L = _l.load()
     C = features.shape[1]
     need = int(L.fnp_sparse_to_dense_workspace_bytes(batch_size, *shape))

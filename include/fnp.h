@@ -596,7 +596,7 @@ int fnp_clipcrop_sample(const void *images, int dtype, int channels, int image_h
                         int out_size, void *crops, fnp_stream_t stream);
 
 /* SparseConvTensor.dense() as used by HeightCompression (height_compression.py:20-24):
- * feats (n,C) -> out (B,C,D,H,W) of the same dtype (viewed as (B, C*D, H, W) by the caller).
+ * feats (n,C) -> out (B,C,D,H,W) of the same dtype (FNP_F32, FNP_BF16 or FNP_F16) (viewed as (B, C*D, H, W) by the caller).
  * With a workspace of fnp_sparse_to_dense_workspace_bytes() (a cell -> row map) every element of
  * `out` is written exactly once, zeros included, in 128-byte segments: `out` need not be zeroed.
  * With workspace == NULL a row-driven scatter runs and `out` must be zero on entry. */
@@ -610,6 +610,17 @@ int fnp_sparse_to_dense(const void *feats, int dtype, const int *coords, const i
 int fnp_sparse_to_dense_fill(const void *feats, int dtype, const int *coords, const int *n_rows, int cap, int C,
                              int B, int D, int H, int W, void *out, const float *fill, void *workspace,
                              int64_t workspace_bytes, fnp_stream_t stream);
+/* The adjoint of fnp_sparse_to_dense (the backward of SparseConvTensor.dense() / HeightCompression): grad_out (B,C,D,H,W),
+ * contiguous -> grad_feats (cap, C), both of `dtype` (FNP_F32, FNP_BF16 or FNP_F16, as the two calls above).  A row r < n
+ * whose (b, z, y, x) lies in the grid gets grad_out[b, :, z, y, x], copied bit for bit; every other row (r >= n, or outside
+ * the grid) gets 0.  Every row of grad_feats is written (it need not be zeroed); grad_out is read only inside its bounds.
+ * No host synchronisation, no atomics, capturable.  The workspace (fnp_sparse_to_dense_workspace_bytes()) is rebuilt by the
+ * call itself as the cell -> row map: the plane-tiled gather reads each element of an occupied 64*VEC-cell tile at most once;
+ * workspace == NULL (or a row size the tile kernel does not take: C * sizeof(T) not a multiple of 4) runs a row-driven
+ * gather.  Coordinates must be unique per site (spconv's contract); duplicates are memory-safe only. */
+int fnp_sparse_to_dense_backward(const void *grad_out, int dtype, const int *coords, const int *n_rows, int cap, int C,
+                                 int B, int D, int H, int W, void *grad_feats, void *workspace,
+                                 int64_t workspace_bytes, fnp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Greedy Box Seeker — replaces hot loops 2-4 of FrustumProposerOG.get_proposals

@@ -13,6 +13,8 @@ ap.add_argument("--dtype", default="bf16")
 ap.add_argument("--sweeps", type=int, default=1, help="10: the density transfusion_lidar.yaml trains on (nuscenes_dataset.yaml:5 MAX_SWEEPS 10): ~300 k points, ~150 k voxels per scene")
 ap.add_argument("--amp", action="store_true", help="the reference's AMP recipe (tools/train_utils/train_utils.py:135-176): autocast(fp16) around the forward, "
                 "GradScaler, unscale_, clip_grad_norm_(10), scaler.step / update")
+ap.add_argument("--through-bev", action="store_true", help="also time the step with the loss (mean of squares) on spatial_features_2d: HeightCompression "
+                "(differentiable densify) + BaseBEVBackbone in train mode (the reference's torch modules, transfusion_lidar.yaml's BEV config)")
 args = ap.parse_args()
 dev = torch.device("cuda", 0); B = args.batch
 grid = np.round((np.array(syn.POINT_CLOUD_RANGE[3:]) - np.array(syn.POINT_CLOUD_RANGE[:3])) / np.array(syn.VOXEL_SIZE)).astype(int)
@@ -60,6 +62,44 @@ def step(all_outputs=True):
     scaler.update()
 
 net.train()
+bev_keys = {}
+if args.through_bev:
+    from findnpropagate_amd.backbones_2d import BaseBEVBackbone, HeightCompression
+    hc = HeightCompression({"NUM_BEV_FEATURES": 256})
+    bev = BaseBEVBackbone({"LAYER_NUMS": [5, 5], "LAYER_STRIDES": [1, 2], "NUM_FILTERS": [128, 256], "UPSAMPLE_STRIDES": [1, 2],
+                           "NUM_UPSAMPLE_FILTERS": [256, 256], "USE_CONV_FOR_NO_STRIDE": True}, 256).to(dev).train()
+    params = list(net.parameters()) + list(bev.parameters())
+    opt_bev = torch.optim.SGD(params, lr=1e-4)
+    sc_bev = torch.amp.GradScaler("cuda", init_scale=2.0 ** 12) if args.amp else None
+
+    def bev_step():
+        opt_bev.zero_grad(set_to_none=True)
+        with torch.autocast("cuda", dtype=torch.float16, enabled=args.amp):
+            out = net(bd())
+            loss = (bev(hc(dict(out)))["spatial_features_2d"].float() ** 2).mean()
+        if sc_bev is None:
+            loss.backward(); opt_bev.step()
+            return
+        sc_bev.scale(loss).backward()
+        sc_bev.unscale_(opt_bev)
+        torch.nn.utils.clip_grad_norm_(params, 10.0)
+        sc_bev.step(opt_bev)
+        sc_bev.update()
+
+    def bev_only():   # the 2D part alone: the same step on a detached copy of the encoded tensor's dense map
+        opt_bev.zero_grad(set_to_none=True)
+        with torch.autocast("cuda", dtype=torch.float16, enabled=args.amp):
+            loss = (bev({"spatial_features": sf})["spatial_features_2d"].float() ** 2).mean()
+        (loss if sc_bev is None else sc_bev.scale(loss)).backward()
+
+    ms_bev = timed(bev_step, args.reps)
+    assert all(p.grad is not None for p in net.parameters()), "the BEV loss did not reach every backbone parameter"
+    with torch.no_grad():
+        sf = hc(dict(net(bd())))["spatial_features"].clone()
+    ms_bev_only = timed(bev_only, args.reps)
+    bev_keys = {"train_step_through_bev_ms": round(ms_bev, 2), "bev_2d_step_alone_ms": round(ms_bev_only, 2),
+                "scenes_per_s_train_through_bev": round(B / ms_bev * 1e3, 1)}
+    del sf
 ms_step = timed(step, args.reps)
 ms_step_enc = timed(lambda: step(False), args.reps)
 # what the stand-in loss itself costs (forward + backward of the five mean-of-squares on detached copies of the outputs)
@@ -80,4 +120,4 @@ print(json.dumps({"batch": B, "sweeps": args.sweeps, "amp": bool(args.amp), "poi
                   "train_step_ms": round(ms_step, 2),
                   "train_step_ms_loss_on_encoded_tensor_only": round(ms_step_enc, 2), "stand_in_loss_alone_ms": round(ms_loss, 2),
                   "module_forward_ms": round(ms_fwd_train, 2),
-                  "fused_eval_forward_ms": round(ms_fwd_eval, 2), "scenes_per_s_train": round(B / ms_step * 1e3, 1)}))
+                  "fused_eval_forward_ms": round(ms_fwd_eval, 2), "scenes_per_s_train": round(B / ms_step * 1e3, 1), **bev_keys}))
