@@ -1,3 +1,3 @@
-from . import data_augmentor, pseudo_loader
+from . import data_augmentor, database_sampler, pseudo_loader
 
-__all__ = ["data_augmentor", "pseudo_loader"]
+__all__ = ["data_augmentor", "database_sampler", "pseudo_loader"]

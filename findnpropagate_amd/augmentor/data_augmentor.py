@@ -16,14 +16,19 @@ Two modes:
             op program is recorded in data_dict['prep_program'] ((K, 4) f32 rows {op, a, b, c}, one per drawn op in config
             order), for sparse.prepare_points to apply on the device in front of the voxeliser.  The collate stacks the
             programs with stack_programs() to (B, K, 4).
-Any other augmentor (gt_sampling, random_local_*, image and pseudo-label ops) raises NotImplementedError naming itself, unless
-DISABLE_AUG_LIST lists it.
+gt_sampling builds database_sampler.DataBaseSampler as the reference does (data_augmentor.py:42-49) and runs at its place in the
+queue.  Host mode cuts the scene points inside the sampled boxes here; deferred mode puts the object rows in front of the scene
+rows and records the cut (data_dict['prep_cut_boxes'], data_dict['prep_cut_from']) for sparse.prepare_points, which cuts before
+it applies the program: a deferred gt_sampling after a recorded world op raises ValueError.  The collate stacks the cuts with
+stack_cut_boxes().  Any other augmentor (random_local_*, image and pseudo-label ops) raises NotImplementedError naming itself,
+unless DISABLE_AUG_LIST lists it.
 """
 from functools import partial
 
 import numpy as np
 import torch
 
+from . import database_sampler
 from .pseudo_loader import rotate_points_along_z
 
 OP_NONE, OP_FLIP_X, OP_FLIP_Y, OP_ROTATE, OP_SCALE, OP_TRANSLATE = range(6)
@@ -86,6 +91,16 @@ def stack_programs(programs, steps=None):
     return out
 
 
+def stack_cut_boxes(boxes_list, cut_from_list):
+    """Collate: per-scene enlarged cut boxes (M_b, 7) and leading object row counts -> records (sum M_b, 8) f32
+    (fnp_host_cut_records), box offsets (B+1,) int32 and cut_from (B,) int32: the `cut` of sparse.prepare_points"""
+    boxes = [np.asarray(b, np.float32).reshape(-1, 7) for b in boxes_list]
+    off = np.zeros(len(boxes) + 1, np.int32)
+    off[1:] = np.cumsum([b.shape[0] for b in boxes])
+    records = database_sampler.cut_records(np.concatenate(boxes, 0) if boxes else np.zeros((0, 7), np.float32))
+    return records, off, np.asarray(cut_from_list, np.int32).reshape(len(boxes))
+
+
 def _get(config, key, default=None):
     if isinstance(config, dict):
         return config.get(key, default)
@@ -141,7 +156,8 @@ class DataAugmentor(object):
             name = _get(cur_cfg, 'NAME')
             if name in disabled:
                 continue
-            if name not in ('random_world_flip', 'random_world_rotation', 'random_world_scaling', 'random_world_translation'):
+            if name not in ('gt_sampling', 'random_world_flip', 'random_world_rotation', 'random_world_scaling',
+                            'random_world_translation'):
                 raise NotImplementedError(f"DataAugmentor.{name} is not implemented in this build (list it in DISABLE_AUG_LIST)")
             self.data_augmentor_queue.append(getattr(self, name)(config=cur_cfg))
 
@@ -155,6 +171,19 @@ class DataAugmentor(object):
 
     def __setstate__(self, d):
         self.__dict__.update(d)
+
+    def gt_sampling(self, data_dict=None, config=None):
+        if data_dict is None:
+            if self.root_path is None or _get(config, 'DB_INFO_PATH') is None:
+                raise NotImplementedError("DataAugmentor.gt_sampling needs a database: root_path and DB_INFO_PATH")
+            db_sampler = database_sampler.DataBaseSampler(root_path=self.root_path, sampler_cfg=config,
+                                                          class_names=self.class_names, logger=self.logger,
+                                                          deferred=self.deferred)
+            return partial(self.gt_sampling, config=db_sampler)
+        if self.deferred and PROGRAM_KEY in data_dict:
+            raise ValueError("a deferred gt_sampling must come before the world ops: the device cuts the scene points "
+                             "before it applies their program")
+        return config(data_dict)
 
     def _record(self, data_dict, op, a=0.0, b=0.0, c=0.0):
         """deferred mode: append one step to the scene's program"""

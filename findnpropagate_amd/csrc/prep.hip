@@ -16,6 +16,15 @@
 //   FNP_SHUFFLE_DEVICE   o_b + feistel_b(k)                       (a keyed bijection of [0, m_b); not numpy's permutation)
 //   FNP_SHUFFLE_EXPLICIT j where perm[j] = k, j in [o_b, o_b + m_b)  (out[j] = kept[perm[j]]: the reference's order, bit for bit)
 // No atomics, no host synchronisation; every row count is read from device memory.
+//
+// fnp_prepare_points_cut adds gt_sampling's cut (DataBaseSampler.add_sampled_boxes_to_scene, database_sampler.py:367-452) to
+// the mark: row i of scene b is dropped when i >= off[b] + cut_from[b] (the pasted object rows lead the scene and are never cut)
+// and the row, before its program moves it, lies inside one of the scene's records [cut_offsets[b], cut_offsets[b+1]) (boxcut.h).
+// The two entry points share every kernel; the cut is a compile-time flag of the mark, and the no-cut instantiation is the
+// mark as it was.
+#include <vector>
+
+#include "boxcut.h"
 #include "rankgrid.h"
 
 namespace {
@@ -123,14 +132,49 @@ __device__ __forceinline__ bool kept_point(const float *__restrict__ pts, int C,
     return in_range(r, x, y);
 }
 
+struct CutArgs {
+    const float *rec;   // (M, 8) records, boxcut.h
+    const int *off;     // (B+1) scene b owns records [off[b], off[b+1])
+    const int *from;    // (B)   scene b's rows [0, from[b]) are never cut
+};
+
+// Is row i (raw x, y, z) of scene b cut?  A wave whose live lanes lie in one scene walks that scene's records with wave-uniform
+// loads and leaves the walk once no lane needs another box; a wave that straddles two scenes walks each lane's own records.
+__device__ __forceinline__ bool cut_row(const CutArgs &cut, const int *__restrict__ off, int b, int i, float x, float y, float z) {
+    const bool test = i >= off[b] + cut.from[b];
+    bool inside = false;
+    const int b0 = __builtin_amdgcn_readfirstlane(b);
+    if (__ballot(b != b0) == 0) {
+        const int k1 = cut.off[b0 + 1];
+        for (int k = cut.off[b0]; k < k1; ++k) {
+            if (__ballot(test && !inside) == 0) break;
+            const FnpCutBox bx = fnp_cut_box(cut.rec + (size_t)k * 8);
+            if (test && !inside) inside = fnp_cut_inside(bx, x, y, z);
+        }
+    } else if (test) {
+        const int k1 = cut.off[b + 1];
+        for (int k = cut.off[b]; k < k1 && !inside; ++k) inside = fnp_cut_inside(fnp_cut_box(cut.rec + (size_t)k * 8), x, y, z);
+    }
+    return inside;
+}
+
+template <bool kCut>
 __global__ __launch_bounds__(kThreads) void prep_mark_kernel(const float *__restrict__ pts, int n, int C, const int *__restrict__ off, int B,
-                                                             const float *__restrict__ prog, int K, XyRange r,
+                                                             const float *__restrict__ prog, int K, XyRange r, CutArgs cut,
                                                              unsigned long long *__restrict__ mask, int *__restrict__ cnt) {
     __shared__ int wcnt[kWaves];
     const int i = blockIdx.x * kThreads + threadIdx.x;
     const int lo = off[0], hi = off[B];
     bool keep = false;
-    if (i < n && i >= lo && i < hi) keep = kept_point(pts, C, i, scene_of_wave(off, B, i), prog, K, r);
+    if (i < n && i >= lo && i < hi) {
+        const int b = scene_of_wave(off, B, i);
+        if constexpr (kCut) {
+            const float *p = pts + (size_t)i * C;
+            keep = !cut_row(cut, off, b, i, p[0], p[1], p[2]) && kept_point(pts, C, i, b, prog, K, r);
+        } else {
+            keep = kept_point(pts, C, i, b, prog, K, r);
+        }
+    }
     const unsigned long long bal = __ballot(keep);
     const int wave = threadIdx.x >> 6;
     if (fnp_lane() == 0) {
@@ -260,15 +304,17 @@ extern "C" int64_t fnp_prepare_points_workspace_bytes(int64_t n_points) {
     return carve(w, nullptr, n_points > 0 ? n_points : 1);
 }
 
-extern "C" int fnp_prepare_points(const float *points, int64_t n_points, int num_features, const int *batch_offsets, int batch_size,
-                                  const float *program, int program_steps, double x_min, double y_min, double x_max, double y_max,
-                                  int shuffle_mode, const int *perm, int64_t n_perm, uint64_t seed, float pad,
-                                  void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream) {
+template <bool kCut>
+static int prepare_points(const float *points, int64_t n_points, int num_features, const int *batch_offsets, int batch_size,
+                          const float *program, int program_steps, CutArgs cut, double x_min, double y_min, double x_max, double y_max,
+                          int shuffle_mode, const int *perm, int64_t n_perm, uint64_t seed, float pad,
+                          void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream) {
     hipStream_t s = (hipStream_t)stream;
     if (n_points < 0 || n_points > 0x7fffffffll || num_features < 3 || batch_size <= 0 || !batch_offsets || !out_offsets) return FNP_ERR_ARG;
     if (program_steps < 0 || program_steps > FNP_PREP_MAX_STEPS || (program_steps > 0 && !program) || ((uintptr_t)program & 15)) return FNP_ERR_ARG;
     if (shuffle_mode != FNP_SHUFFLE_NONE && shuffle_mode != FNP_SHUFFLE_DEVICE && shuffle_mode != FNP_SHUFFLE_EXPLICIT) return FNP_ERR_ARG;
     if (shuffle_mode == FNP_SHUFFLE_EXPLICIT && (n_perm < 0 || (n_perm > 0 && !perm))) return FNP_ERR_ARG;
+    if (kCut && (!cut.off || !cut.from || ((uintptr_t)cut.rec & 3))) return FNP_ERR_ARG;
     const int n = (int)n_points, B = batch_size, C = num_features;
     if (n == 0) {   // no rows: every scene keeps nothing
         return fnp_fill_words(out_offsets, (long long)B + 1, 0u, s);
@@ -280,7 +326,8 @@ extern "C" int fnp_prepare_points(const float *points, int64_t n_points, int num
     const float *prog = program_steps > 0 ? program : nullptr;
     const int G = fnp_divup(n, kThreads);
 
-    hipLaunchKernelGGL(prep_mark_kernel, dim3(G), dim3(kThreads), 0, s, points, n, C, batch_offsets, B, prog, program_steps, r, w.mask, w.cnt);
+    hipLaunchKernelGGL(prep_mark_kernel<kCut>, dim3(G), dim3(kThreads), 0, s, points, n, C, batch_offsets, B, prog, program_steps, r, cut,
+                       w.mask, w.cnt);
     FNP_LAUNCH_CHECK();
     int rc = fnp_scan::int32(w.cnt, G, w.base, w.total, w.scan_ws, s);
     if (rc) return rc;
@@ -296,5 +343,64 @@ extern "C" int fnp_prepare_points(const float *points, int64_t n_points, int num
                        (unsigned long long)seed, (const unsigned long long *)w.mask, (const int *)w.base, (const int *)w.inv,
                        (const int *)out_offsets, pad, out_points);
     FNP_LAUNCH_CHECK();
+    return FNP_OK;
+}
+
+extern "C" int fnp_prepare_points(const float *points, int64_t n_points, int num_features, const int *batch_offsets, int batch_size,
+                                  const float *program, int program_steps, double x_min, double y_min, double x_max, double y_max,
+                                  int shuffle_mode, const int *perm, int64_t n_perm, uint64_t seed, float pad,
+                                  void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream) {
+    return prepare_points<false>(points, n_points, num_features, batch_offsets, batch_size, program, program_steps, CutArgs{},
+                                 x_min, y_min, x_max, y_max, shuffle_mode, perm, n_perm, seed, pad, workspace, workspace_bytes,
+                                 out_points, out_offsets, stream);
+}
+
+extern "C" int fnp_prepare_points_cut(const float *points, int64_t n_points, int num_features, const int *batch_offsets, int batch_size,
+                                      const float *program, int program_steps, const float *cut_records, const int *cut_offsets,
+                                      const int *cut_from, double x_min, double y_min, double x_max, double y_max,
+                                      int shuffle_mode, const int *perm, int64_t n_perm, uint64_t seed, float pad,
+                                      void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream) {
+    return prepare_points<true>(points, n_points, num_features, batch_offsets, batch_size, program, program_steps,
+                                CutArgs{cut_records, cut_offsets, cut_from}, x_min, y_min, x_max, y_max, shuffle_mode, perm, n_perm,
+                                seed, pad, workspace, workspace_bytes, out_points, out_offsets, stream);
+}
+
+// ---- host entry points of the cut (DataLoader workers: no device, no stream) ----
+extern "C" int fnp_host_cut_records(const float *boxes, int m, float *records) {
+    if (m < 0 || (m > 0 && (!boxes || !records))) return FNP_ERR_ARG;
+    for (int j = 0; j < m; ++j) {
+        const float *b = boxes + (size_t)j * 7;
+        float *q = records + (size_t)j * 8;
+        for (int c = 0; c < 6; ++c) q[c] = b[c];
+        q[6] = cosf(-b[6]);
+        q[7] = sinf(-b[6]);
+    }
+    return FNP_OK;
+}
+
+// remove_points_in_boxes3d's keep mask (points_in_boxes_cpu(...).sum(0) == 0) without the (M, N) matrix: a point leaves the box
+// loop at its first box.  The prefilter |sx| > R or |sy| > R, R = 1.001 * (hx + hy) + 1e-3, drops no point the test keeps: for
+// a point inside, the f32 rotation (l, two products and a sum, relative error < 2^-22 of |sx| + |sy|; c^2 + s^2 within 2^-22 of
+// 1) bounds max(|sx|, |sy|) <= |(sx, sy)| < (hx + hy) * (1 + 1e-6).  A NaN passes the prefilter and fails the test.
+extern "C" int fnp_host_points_outside_boxes(const float *points, int64_t n, int num_features, const float *records, int m,
+                                             unsigned char *keep) {
+    if (n < 0 || m < 0 || num_features < 3 || (n > 0 && (!points || !keep)) || (n > 0 && m > 0 && !records)) return FNP_ERR_ARG;
+    std::vector<FnpCutBox> bx((size_t)m);
+    std::vector<float> reach((size_t)m);
+    for (int j = 0; j < m; ++j) {
+        bx[j] = fnp_cut_box(records + (size_t)j * 8);
+        reach[j] = (float)(1.001 * (bx[j].hx + bx[j].hy) + 1e-3);
+    }
+    for (int64_t i = 0; i < n; ++i) {
+        const float *p = points + (size_t)i * num_features;
+        const float x = p[0], y = p[1], z = p[2];
+        bool inside = false;
+        for (int j = 0; j < m && !inside; ++j) {
+            const FnpCutBox &b = bx[j];
+            if (fabsf(x - b.cx) > reach[j] || fabsf(y - b.cy) > reach[j]) continue;
+            inside = fnp_cut_inside(b, x, y, z);
+        }
+        keep[i] = inside ? 0 : 1;
+    }
     return FNP_OK;
 }

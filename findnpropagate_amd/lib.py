@@ -125,6 +125,10 @@ SIGNATURES = {
     "fnp_prepare_points_workspace_bytes": (c_int64, [c_int64]),
     "fnp_prepare_points": (c_int, [P, c_int64, c_int, P, c_int, P, c_int, c_double, c_double, c_double, c_double,
                                    c_int, P, c_int64, c_uint64, c_float, P, c_int64, P, P, P]),
+    "fnp_host_cut_records": (c_int, [P, c_int, P]),
+    "fnp_host_points_outside_boxes": (c_int, [P, c_int64, c_int, P, c_int, P]),
+    "fnp_prepare_points_cut": (c_int, [P, c_int64, c_int, P, c_int, P, c_int, P, P, P, c_double, c_double, c_double, c_double,
+                                       c_int, P, c_int64, c_uint64, c_float, P, c_int64, P, P, P]),
     "fnp_rulebook_subm": (c_int, [P, P, c_int, POINTER(ConvGeom), POINTER(RankGridC), P, P]),
     "fnp_rulebook_strided": (c_int, [P, P, c_int, POINTER(ConvGeom), POINTER(RankGridC), POINTER(RankGridC),
                                      P, P, c_int, P, P, c_int64, P]),

@@ -198,7 +198,7 @@ def stage_points(points, batch_offsets, dst_points, dst_offsets, n_prev, pad):
 PREP_PAD = 1.0e9   # rows behind the kept points of prepare_points: outside every range, dropped by the voxeliser
 
 
-def prepare_points(points, batch_offsets, batch_size, program, point_cloud_range, shuffle=None, seed=0, out=None):
+def prepare_points(points, batch_offsets, batch_size, program, point_cloud_range, shuffle=None, seed=0, out=None, cut=None):
     """World augmentation + range mask + point shuffle of a batch on the device, in front of voxelize (fnp_prepare_points).
 
     points (N,C) f32 device, scenes concatenated; batch_offsets (B+1,) int32 device.
@@ -208,6 +208,10 @@ def prepare_points(points, batch_offsets, batch_size, program, point_cloud_range
     shuffle: None (kept rows in order), "device" (a keyed permutation per scene, reproducible for a seed; not numpy's), or a (K,)
     int32 device tensor: scene b's slice [o_b, o_b + m_b) holds the numpy permutation of its m_b kept rows (the reference's order).
     out: a dict returned by an earlier call with the same N, C and B, whose buffers are reused (a captured graph's static outputs).
+    cut: gt_sampling's cut (fnp_prepare_points_cut), or None.  (records (M, 8) f32, box_offsets (B+1,) int32, cut_from (B,) int32),
+    device tensors (augmentor.data_augmentor.stack_cut_boxes of what DataAugmentor records in deferred mode): row i of scene b is
+    dropped when i >= batch_offsets[b] + cut_from[b] and the raw row lies inside one of records[box_offsets[b]:box_offsets[b+1]],
+    before the program moves it (the host mode's remove_points_in_boxes3d, bit for bit).
 
     Returns dict(points (N,C) f32: the kept rows scene after scene, then PREP_PAD rows; batch_offsets (B+1,) int32: the new
     offsets; n (1,) int32: the kept count; batch_size) — points and batch_offsets are what voxelize / forward_points take, over
@@ -245,12 +249,24 @@ def prepare_points(points, batch_offsets, batch_size, program, point_cloud_range
         out.update(batch_offsets=off, n=off[batch_size:], batch_size=batch_size)
     else:
         assert out["points"].shape == (n, C) and out["batch_offsets"].numel() == batch_size + 1 and out["workspace"].numel() >= ws_bytes
-    rc = L.fnp_prepare_points(_l.ptr(points) if n else None, n, C, _l.ptr(batch_offsets), batch_size,
-                              _l.ptr(program) if K else None, K, rng[0], rng[1], rng[3], rng[4],
-                              mode, _l.ptr(perm) if perm is not None and perm.numel() else None, 0 if perm is None else perm.numel(),
-                              int(seed) & 0xFFFFFFFFFFFFFFFF, PREP_PAD, _l.ptr(out["workspace"]), out["workspace"].numel(),
-                              _l.ptr(out["points"]) if n else None, _l.ptr(out["batch_offsets"]), _l.stream())
-    _l.check(rc, "fnp_prepare_points")
+    tail = (rng[0], rng[1], rng[3], rng[4],
+            mode, _l.ptr(perm) if perm is not None and perm.numel() else None, 0 if perm is None else perm.numel(),
+            int(seed) & 0xFFFFFFFFFFFFFFFF, PREP_PAD, _l.ptr(out["workspace"]), out["workspace"].numel(),
+            _l.ptr(out["points"]) if n else None, _l.ptr(out["batch_offsets"]), _l.stream())
+    if cut is None:
+        rc = L.fnp_prepare_points(_l.ptr(points) if n else None, n, C, _l.ptr(batch_offsets), batch_size,
+                                  _l.ptr(program) if K else None, K, *tail)
+        _l.check(rc, "fnp_prepare_points")
+        return out
+    records, box_off, cut_from = cut
+    _l.require_device(records, box_off, cut_from)
+    assert records.dtype == torch.float32 and records.dim() == 2 and records.shape[1] == 8 and records.is_contiguous()
+    assert box_off.dtype == torch.int32 and box_off.numel() == batch_size + 1 and box_off.is_contiguous()
+    assert cut_from.dtype == torch.int32 and cut_from.numel() == batch_size and cut_from.is_contiguous()
+    rc = L.fnp_prepare_points_cut(_l.ptr(points) if n else None, n, C, _l.ptr(batch_offsets), batch_size,
+                                  _l.ptr(program) if K else None, K,
+                                  _l.ptr(records) if records.numel() else None, _l.ptr(box_off), _l.ptr(cut_from), *tail)
+    _l.check(rc, "fnp_prepare_points_cut")
     return out
 
 

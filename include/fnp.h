@@ -253,6 +253,28 @@ int fnp_prepare_points(const float *points, int64_t n_points, int num_features, 
                        int shuffle_mode, const int *perm, int64_t n_perm, uint64_t seed, float pad,
                        void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream);
 
+/* gt_sampling's cut (DataBaseSampler.add_sampled_boxes_to_scene: box_utils.remove_points_in_boxes3d over the sampled boxes enlarged
+ * by REMOVE_EXTRA_WIDTH, i.e. roiaware_pool3d.cpp points_in_boxes_cpu).  A cut record is 8 f32 {cx, cy, cz, dx, dy, dz, cos(-h),
+ * sin(-h)}; a point is inside when fabsf(z - cz) <= dz / 2.0 and, with the f32 rotation lx = sx*c + sy*(-s), ly = sx*s + sy*c
+ * (sx = x - cx, sy = y - cy), |lx| < dx / 2.0 + 1e-2f and |ly| < dy / 2.0 + 1e-2f, compared in double: the reference's test bit
+ * for bit.  Host and device share that one definition.
+ *
+ * fnp_host_cut_records: boxes (m, 7) f32 host -> records (m, 8) f32 host, cos / sin by the C library's cosf / sinf.
+ * fnp_host_points_outside_boxes: keep[i] = 1 iff point i of points (n, C) f32 host lies in none of the m records (host). */
+int fnp_host_cut_records(const float *boxes, int m, float *records);
+int fnp_host_points_outside_boxes(const float *points, int64_t n, int num_features, const float *records, int m,
+                                  unsigned char *keep);
+
+/* fnp_prepare_points with the cut in front of the program: row i of scene b is dropped when i >= off[b] + cut_from[b] and the
+ * raw row lies inside one of the records [cut_offsets[b], cut_offsets[b+1]) of cut_records (device, 4-byte aligned; NULL only
+ * when no scene has a record).  cut_offsets (B+1,) and cut_from (B,) are int32 device arrays.  Same workspace, outputs and
+ * guarantees as fnp_prepare_points: no atomics, no host synchronisation, any number of records per scene, capturable. */
+int fnp_prepare_points_cut(const float *points, int64_t n_points, int num_features, const int *batch_offsets, int batch_size,
+                           const float *program, int program_steps, const float *cut_records, const int *cut_offsets,
+                           const int *cut_from, double x_min, double y_min, double x_max, double y_max,
+                           int shuffle_mode, const int *perm, int64_t n_perm, uint64_t seed, float pad,
+                           void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream);
+
 /* ------------------------------------------------------------------------------------------
  * Rulebooks — replace spconv's indice-pair generation for SubMConv3d / SparseConv3d
  * (call sites pcdet/models/backbones_3d/spconv_backbone.py:12-17,39-46,193-234).

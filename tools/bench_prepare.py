@@ -3,8 +3,11 @@
 
 device: sparse.prepare_points (fnp_prepare_points, device shuffle and explicit-permutation modes), median of HIP-event timed
         launches, for B = 4 ten-sweep scenes (~300 k points each) and B = 128 single-sweep scenes (~30 k points each);
+        with gt_sampling's cut (fnp_prepare_points_cut, device shuffle) of 39 boxes per ten-sweep scene and 25 per single-sweep
+        scene, the boxes centred on scene points with nuScenes class sizes (cut_us against no_cut_us, the same launch without it);
 host:   the same work as the reference does it per scene in DataLoader workers (DataAugmentor host mode + mask_points_by_range +
-        np.random.permutation), wall time per batch with 1 worker process and with 16, torch at one thread per process.
+        np.random.permutation), wall time per batch with 1 worker process and with 16, torch at one thread per process; and the
+        host-mode cut (fnp_host_points_outside_boxes + the compaction) per scene, median, in one worker.
 Host timings run first, in forked workers, before this process touches the GPU.
 
     python tools/bench_prepare.py [--reps 50]
@@ -28,6 +31,38 @@ CFG = [dict(NAME='random_world_flip', ALONG_AXIS_LIST=['x', 'y']),
        dict(NAME='random_world_scaling', WORLD_SCALE_RANGE=[0.9, 1.1]),
        dict(NAME='random_world_translation', NOISE_TRANSLATE_STD=[0.5, 0.5, 0.5])]
 _SCENES = None
+_BOXES = None
+CUT_BOXES = {"b4_x_300k": 39, "b128_x_30k": 25}
+SIZES = [(4.6, 1.9, 1.7), (7.0, 2.5, 3.0), (6.5, 2.8, 3.2), (11.0, 2.9, 3.5), (12.0, 2.9, 3.8), (0.5, 2.5, 1.0), (2.1, 0.8, 1.5),
+         (1.7, 0.6, 1.3), (0.7, 0.7, 1.8), (0.4, 0.4, 1.0)]
+
+
+def cut_boxes(scene, n, seed):
+    """n (7,) f32 boxes centred on scene points, class sizes +-15 %, standing on the ground"""
+    rng = np.random.default_rng(seed)
+    b = np.zeros((n, 7), np.float32)
+    b[:, 0:2] = scene[rng.integers(0, scene.shape[0], n), 0:2]
+    b[:, 3:6] = np.array([SIZES[k % len(SIZES)] for k in range(n)]) * rng.uniform(0.85, 1.15, (n, 3))
+    b[:, 2] = syn.GROUND_Z + b[:, 5] / 2
+    b[:, 6] = rng.uniform(-np.pi, np.pi, n)
+    return b
+
+
+def _host_cut_scene(b):
+    from findnpropagate_amd.augmentor.database_sampler import cut_records, points_outside_boxes
+
+    t = time.perf_counter()
+    p = _SCENES[b]
+    p = p[points_outside_boxes(p[:, 0:3], cut_records(_BOXES[b]))]
+    return time.perf_counter() - t, int(p.shape[0])
+
+
+def host_cut_time(scenes, boxes, reps=3):
+    global _SCENES, _BOXES
+    _SCENES, _BOXES = scenes, boxes
+    with mp.get_context("fork").Pool(1, initializer=_init_worker) as pool:
+        ts = [t for _ in range(reps) for t, _ in pool.map(_host_cut_scene, range(len(scenes)), chunksize=1)]
+    return float(np.median(ts)) * 1e3
 
 
 def _init_worker():
@@ -62,6 +97,41 @@ def host_time(scenes, workers, reps=3):
             pool.map(_host_scene, [(b, 100 * r + b) for b in range(len(scenes))], chunksize=1)
             best = min(best, time.perf_counter() - t)
     return best * 1e3
+
+
+def device_cut_time(scenes, boxes, reps):
+    import torch
+
+    from findnpropagate_amd import sparse as S
+    from findnpropagate_amd.augmentor.data_augmentor import DataAugmentor, PROGRAM_KEY, stack_cut_boxes, stack_programs
+
+    dev = torch.device("cuda", 0)
+    progs = []
+    for b, s in enumerate(scenes):
+        np.random.seed(b)
+        progs.append(DataAugmentor(None, CFG, [], deferred=True).forward(dict(points=s, gt_boxes=np.zeros((0, 9), np.float32)))[PROGRAM_KEY])
+    pts = torch.from_numpy(np.concatenate(scenes)).to(dev)
+    off = torch.from_numpy(np.concatenate([[0], np.cumsum([s.shape[0] for s in scenes])]).astype(np.int32)).to(dev)
+    prog = torch.from_numpy(stack_programs(progs)).to(dev)
+    cut = tuple(torch.from_numpy(a).to(dev) for a in stack_cut_boxes(boxes, [0] * len(scenes)))
+    B = len(scenes)
+    res = {}
+    for name, c in (("no_cut", None), ("cut", cut)):
+        out = S.prepare_points(pts, off, B, prog, syn.POINT_CLOUD_RANGE, shuffle="device", cut=c)
+        for _ in range(5):
+            S.prepare_points(pts, off, B, prog, syn.POINT_CLOUD_RANGE, shuffle="device", cut=c, out=out)
+        ts = []
+        for _ in range(reps):
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            S.prepare_points(pts, off, B, prog, syn.POINT_CLOUD_RANGE, shuffle="device", cut=c, out=out)
+            z.record()
+            z.synchronize()
+            ts.append(a.elapsed_time(z) * 1e3)
+        res[name + "_us"] = round(float(np.median(ts)), 1)
+        res[name + "_kept"] = int(out["n"].item())
+    res["cut_boxes_per_scene"] = int(boxes[0].shape[0])
+    return res
 
 
 def device_time(scenes, reps):
@@ -110,11 +180,15 @@ def main():
     pts, off = syn.make_batch(range(128))
     single = [pts[off[b]:off[b + 1]] for b in range(128)]
     out = {"metric": "prepare_points"}
+    boxes = {name: [cut_boxes(s, CUT_BOXES[name], 1000 + b) for b, s in enumerate(scenes)]
+             for name, scenes in (("b4_x_300k", sweeps), ("b128_x_30k", single))}
     for name, scenes in (("b4_x_300k", sweeps), ("b128_x_30k", single)):
         out[name] = {"host_1_worker_ms": round(host_time(scenes, 1), 2),
-                     f"host_{a.workers}_workers_ms": round(host_time(scenes, a.workers), 2)}
+                     f"host_{a.workers}_workers_ms": round(host_time(scenes, a.workers), 2),
+                     "host_cut_ms_per_scene": round(host_cut_time(scenes, boxes[name]), 2)}
     for name, scenes in (("b4_x_300k", sweeps), ("b128_x_30k", single)):
         out[name].update(device_time(scenes, a.reps))
+        out[name].update(device_cut_time(scenes, boxes[name], a.reps))
     print(json.dumps(out))
 
 
