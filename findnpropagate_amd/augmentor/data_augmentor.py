@@ -20,8 +20,17 @@ gt_sampling builds database_sampler.DataBaseSampler as the reference does (data_
 queue.  Host mode cuts the scene points inside the sampled boxes here; deferred mode puts the object rows in front of the scene
 rows and records the cut (data_dict['prep_cut_boxes'], data_dict['prep_cut_from']) for sparse.prepare_points, which cuts before
 it applies the program: a deferred gt_sampling after a recorded world op raises ValueError.  The collate stacks the cuts with
-stack_cut_boxes().  Any other augmentor (random_local_*, image and pseudo-label ops) raises NotImplementedError naming itself,
-unless DISABLE_AUG_LIST lists it.
+stack_cut_boxes().
+load_frustum_pseudos, load_selftrain_pseudos and unknowns_copy_paste build and share one pseudo_loader.PseudoLoader with the
+reference's constructor semantics (data_augmentor.py:327-360) and delegate to it.  The two load_* entries touch boxes only and
+run the same in both modes.  unknowns_copy_paste feeds the sampler's queue from the scene and appends the pasted object rows
+behind every scene row.  In deferred mode, after a deferred gt_sampling, the queue is fed only from the rows that survive the
+pending cut (the rows below prep_cut_from, and the rows inside no cut box): host mode's cut scene, row for row, so the queue,
+the np.random draws and the pasted rows are the host mode's.  It then records data_dict['prep_cut_to'], the rows in front of
+the first pasted row, so that the device cut spares the pasted rows; stack_cut_boxes(..., cut_to_list) makes the 4-tuple cut
+of sparse.prepare_points.  A deferred unknowns_copy_paste after a recorded world op raises ValueError.
+Any other augmentor (random_local_*, frustum dropout, image ops) raises NotImplementedError naming itself, unless
+DISABLE_AUG_LIST lists it.
 """
 from functools import partial
 
@@ -29,11 +38,15 @@ import numpy as np
 import torch
 
 from . import database_sampler
-from .pseudo_loader import rotate_points_along_z
+from .pseudo_loader import PseudoLoader, rotate_points_along_z
 
 OP_NONE, OP_FLIP_X, OP_FLIP_Y, OP_ROTATE, OP_SCALE, OP_TRANSLATE = range(6)
 MAX_STEPS = 6   # FNP_PREP_MAX_STEPS (include/fnp.h)
 PROGRAM_KEY = 'prep_program'
+CUT_TO_KEY = 'prep_cut_to'
+CUT_TO_END = 0x7fffffff   # a cut_to that reaches the end of the scene
+SUPPORTED = ('gt_sampling', 'load_frustum_pseudos', 'load_selftrain_pseudos', 'unknowns_copy_paste', 'random_world_flip',
+             'random_world_rotation', 'random_world_scaling', 'random_world_translation')
 
 
 def limit_period(val, offset=0.5, period=np.pi):
@@ -91,14 +104,20 @@ def stack_programs(programs, steps=None):
     return out
 
 
-def stack_cut_boxes(boxes_list, cut_from_list):
+def stack_cut_boxes(boxes_list, cut_from_list, cut_to_list=None):
     """Collate: per-scene enlarged cut boxes (M_b, 7) and leading object row counts -> records (sum M_b, 8) f32
-    (fnp_host_cut_records), box offsets (B+1,) int32 and cut_from (B,) int32: the `cut` of sparse.prepare_points"""
+    (fnp_host_cut_records), box offsets (B+1,) int32 and cut_from (B,) int32: the `cut` of sparse.prepare_points.
+    With cut_to_list (per scene data_dict['prep_cut_to'], or None where the scene recorded none), also cut_to (B,) int32, None
+    -> CUT_TO_END: the 4-tuple cut."""
     boxes = [np.asarray(b, np.float32).reshape(-1, 7) for b in boxes_list]
     off = np.zeros(len(boxes) + 1, np.int32)
     off[1:] = np.cumsum([b.shape[0] for b in boxes])
     records = database_sampler.cut_records(np.concatenate(boxes, 0) if boxes else np.zeros((0, 7), np.float32))
-    return records, off, np.asarray(cut_from_list, np.int32).reshape(len(boxes))
+    cut_from = np.asarray(cut_from_list, np.int32).reshape(len(boxes))
+    if cut_to_list is None:
+        return records, off, cut_from
+    cut_to = np.array([CUT_TO_END if t is None else int(t) for t in cut_to_list], np.int32).reshape(len(boxes))
+    return records, off, cut_from, cut_to
 
 
 def _get(config, key, default=None):
@@ -156,8 +175,7 @@ class DataAugmentor(object):
             name = _get(cur_cfg, 'NAME')
             if name in disabled:
                 continue
-            if name not in ('gt_sampling', 'random_world_flip', 'random_world_rotation', 'random_world_scaling',
-                            'random_world_translation'):
+            if name not in SUPPORTED:
                 raise NotImplementedError(f"DataAugmentor.{name} is not implemented in this build (list it in DISABLE_AUG_LIST)")
             self.data_augmentor_queue.append(getattr(self, name)(config=cur_cfg))
 
@@ -184,6 +202,53 @@ class DataAugmentor(object):
             raise ValueError("a deferred gt_sampling must come before the world ops: the device cuts the scene points "
                              "before it applies their program")
         return config(data_dict)
+
+    def _pseudo_loader(self, config):
+        """PseudoLoader(...) of a load_* entry: the reference's keyword mapping and defaults (data_augmentor.py:329-334)"""
+        return PseudoLoader(known_class_names=_get(config, 'KNOWN_CLASSES'), pseudo_path=_get(config, 'PSEUDO_PATH'),
+                            self_train_path=_get(config, 'SELF_TRAIN_PATH', None), dropout=_get(config, 'DROPOUT', 0.5),
+                            min_score=_get(config, 'MIN_SCORE', None), pseudo_nms_thresh=_get(config, 'PSEUDO_NMS_THRESH', 0.1),
+                            max_selftrain_per_class=_get(config, 'MAX_SELFTRAIN_PER_CLASS', None),
+                            fix_cp=_get(config, 'FIX_CP', None), mom=_get(config, 'MOMENTUM', 0.9),
+                            copy_st_only=_get(config, 'COPY_ST_ONLY', False), sampler_val=_get(config, 'SAMPLER_VAL', True))
+
+    def load_frustum_pseudos(self, data_dict=None, config=None):
+        if data_dict is None:
+            self.pseudo_loader = self._pseudo_loader(config)
+            return partial(self.load_frustum_pseudos, config=config)
+        return self.pseudo_loader.load_frustum_pseudos(data_dict)
+
+    def load_selftrain_pseudos(self, data_dict=None, config=None):
+        if data_dict is None:
+            if getattr(self, 'pseudo_loader', None) is None:   # no frustum pseudos: this entry builds the loader
+                self.pseudo_loader = self._pseudo_loader(config)
+            return partial(self.load_selftrain_pseudos, config=config)
+        return self.pseudo_loader.load_selftrain_pseudos(data_dict)
+
+    def unknowns_copy_paste(self, data_dict=None, config=None):
+        if data_dict is None:
+            loader = getattr(self, 'pseudo_loader', None)
+            if loader is None:   # (the reference fails here with an AttributeError)
+                raise AttributeError("DataAugmentor.unknowns_copy_paste needs a pseudo loader: list load_frustum_pseudos or "
+                                     "load_selftrain_pseudos before it")
+            sampler = loader.sampler
+            sampler.max_queue_size_per_class = _get(config, 'MAX_QUEUE_SIZE', sampler.max_queue_size_per_class)
+            sampler.queue_metric = _get(config, 'QUEUE_METRIC', sampler.queue_metric)
+            sampler.trans_noise = _get(config, 'TRANS_NOISE', sampler.trans_noise)
+            sampler.rot_noise = _get(config, 'ROT_NOISE', sampler.rot_noise)
+            sampler.timestamp = _get(config, 'TIMESTAMP', sampler.timestamp)
+            return partial(self.unknowns_copy_paste, config=config)
+        if self.deferred and PROGRAM_KEY in data_dict:
+            raise ValueError("a deferred unknowns_copy_paste must come before the world ops: the rows it appends are not "
+                             "transformed, and the program applies to every row")
+        if not (self.deferred and database_sampler.CUT_BOXES_KEY in data_dict):
+            return self.pseudo_loader.copy_and_paste(data_dict)
+        n_scene = int(data_dict['points'].shape[0])
+        cut = (database_sampler.cut_records(data_dict[database_sampler.CUT_BOXES_KEY]),
+               int(data_dict[database_sampler.CUT_FROM_KEY]), n_scene)
+        data_dict = self.pseudo_loader.copy_and_paste(data_dict, cut=cut)
+        data_dict[CUT_TO_KEY] = n_scene
+        return data_dict
 
     def _record(self, data_dict, op, a=0.0, b=0.0, c=0.0):
         """deferred mode: append one step to the scene's program"""

@@ -8,6 +8,8 @@ of the `.pth` files the extraction writes.  Same name
   read_pseudo_file      :574-603  the `.pth` reader of PseudoLoader.load_pseudos (format written by
                                   tools/extract_pseudo_labels.py:134-137 / findnpropagate_amd.extract.save_frame)
   points_in_boxes       :270-316  PseudoSampler.points_in_boxes: dense (T, N) membership + box-frame points
+  points_in_boxes_compact         the same membership as counts, row indices and box-frame rows of the rows inside only
+                                  (what PseudoSampler.__call__ keeps of it), optionally without the rows a pending cut drops
 
 The stateful policy around them (EMA score thresholds, per-class quotas, the copy-paste queue: PseudoLoader,
 PseudoSampler, ObjectSample) follows further down in this file."""
@@ -69,6 +71,40 @@ def points_in_boxes(points, boxes3d):
     return in_box.astype(bool), out
 
 
+def points_in_boxes_compact(points, boxes3d, cut=None):
+    """points (N, C) numpy, boxes3d (T, 7+) -> (counts (T,) int64, indices (K,) int32, rows (K, C) f32): box after box, in row
+    order, the rows inside the box and their box-frame rows — the True entries of points_in_boxes' in_box and the matching rows
+    of its box-frame points, bit for bit, without the (T, N) matrices (fnp_host_points_in_boxes_compact).
+    cut: None or (records (M, 8) f32 of database_sampler.cut_records, cut_from, cut_to): rows i with cut_from <= i < cut_to that
+    lie inside one of the records are left out (the rows gt_sampling's pending cut drops); indices still number the rows of
+    `points`."""
+    points = np.ascontiguousarray(points, np.float32)
+    boxes = np.ascontiguousarray(np.asarray(boxes3d)[:, :7], np.float32)
+    N, C = points.shape
+    T = boxes.shape[0]
+    if cut is None:
+        records, lo, hi = np.zeros((0, 8), np.float32), 0, 0
+    else:
+        records, lo, hi = cut
+        records = np.ascontiguousarray(records, np.float32).reshape(-1, 8)
+    counts = np.zeros((T,), np.int32)
+    L = _l.load()
+    cap = max(4096, N // 8)
+    while True:
+        indices = np.empty((cap,), np.int32)
+        rows = np.empty((cap, C), np.float32)
+        rc = L.fnp_host_points_in_boxes_compact(points.ctypes.data if N else None, N, C, boxes.ctypes.data if T else None, T,
+                                                records.ctypes.data if records.shape[0] else None, records.shape[0],
+                                                int(lo), int(hi), counts.ctypes.data if T else None, cap, indices.ctypes.data,
+                                                rows.ctypes.data)
+        if rc == -4:                         # FNP_ERR_WORKSPACE: the counts are complete, the exact size
+            cap = int(counts.sum())
+            continue
+        _l.check(rc, "fnp_host_points_in_boxes_compact")
+        k = int(counts.sum())
+        return counts.astype(np.int64), indices[:k], rows[:k]
+
+
 # ------------------------------------------------------------------------------------------------------------------
 # The stateful half of the pseudo-label mixing (SURVEY.md §8 a25): PseudoLoader.load_pseudos /
 # load_frustum_pseudos / load_selftrain_pseudos / copy_and_paste and the copy-paste queue (PseudoSampler, ObjectSample),
@@ -98,6 +134,16 @@ def rotate_points_along_z(points, angle):
 def _bev_iou(a, b):
     """rotated BEV IoU (n,7) x (m,7) on the host, numpy in / numpy out"""
     return iou3d_nms_utils.boxes_bev_iou_cpu(np.ascontiguousarray(a, np.float32), np.ascontiguousarray(b, np.float32))
+
+
+def _box_frame(rows, box):
+    """rows (n, 5) in the frame of box (7+,): the reference's arithmetic (pseudo_loader.py:282-285), f32 centring, then
+    rotate_points_along_z by -heading in the rounding torch's CPU matmul gives it for a point cloud (the fused form of
+    data_augmentor.rotate_points_fused)"""
+    from .data_augmentor import rotate_points_fused
+    p = np.asarray(rows, np.float32).copy()
+    p[:, :3] = p[:, :3] - np.asarray(box[0:3], np.float32)[None, :]
+    return rotate_points_fused(p, -np.float32(box[6]))
 
 
 class ObjectSample(object):
@@ -191,7 +237,9 @@ class PseudoSampler(object):
     def points_in_boxes(self, points, boxes3d):
         return points_in_boxes(points, boxes3d)
 
-    def __call__(self, batch_dict, pseudo_boxes, pseudo_scores, gt_boxes, sample_buffer_num=5, fix_cp=None):
+    def __call__(self, batch_dict, pseudo_boxes, pseudo_scores, gt_boxes, sample_buffer_num=5, fix_cp=None, cut=None):
+        """cut: None, or gt_sampling's pending cut (records, cut_from, cut_to) of a deferred DataAugmentor: the queue is fed as
+        if the rows it drops were gone already (points_in_boxes_compact); the pasted rows still follow every row."""
         self.calc_seen_per_class(pseudo_boxes, gt_boxes)
         in_queue = {l: len(q) for l, q in self.unknown_queue.items()}
         num_scaled = max(int(gt_boxes.shape[0] * self.known_to_unknown_ratio), pseudo_boxes.shape[0])
@@ -200,8 +248,10 @@ class PseudoSampler(object):
         if pseudo_boxes.size == 0:
             return pseudo_boxes, np.zeros((0), dtype=bool)
         gt_plus_ego = torch.cat((torch.tensor(gt_boxes.copy(), dtype=torch.float32)[:, :7], self.ego_vehicle), dim=0)
-        inside, rel_pts = self.points_in_boxes(cur_points, pseudo_boxes[:, :7])
-        n_in = inside.sum(axis=1)
+        assert cur_points.shape[-1] == 5
+        n_in, idx, _ = points_in_boxes_compact(cur_points, pseudo_boxes[:, :7], cut=cut)
+        first = np.concatenate([[0], np.cumsum(n_in)])
+        rel_pts = lambda i: _box_frame(cur_points[idx[first[i]:first[i + 1]]], pseudo_boxes[i])
         order = np.argsort(-n_in, axis=0) if self.queue_metric == 'num_pts' else np.argsort(-pseudo_scores, axis=0)
         max_per_unknown = gt_boxes.shape[0] / max(len(self.known_class_labels), 1)
         seen = {l: 0 for l in self.unknown_class_labels}
@@ -219,14 +269,14 @@ class PseudoSampler(object):
             queue, conf = self.unknown_queue[lbl], pseudo_scores[i]
             if in_queue[lbl] >= self.max_queue_size_per_class:
                 if self.queue_metric == 'num_pts':          # replace the sparsest object
-                    queue[int(np.argmin([o.num_points for o in queue]))] = ObjectSample(rel_pts[i, inside[i]], box.copy(), conf=conf)
+                    queue[int(np.argmin([o.num_points for o in queue]))] = ObjectSample(rel_pts(i), box.copy(), conf=conf)
                 else:                                       # replace the least confident one, if this one beats it
                     confs = np.array([o.conf for o in queue])
                     j = int(np.argmin(confs))
                     if conf > confs[j]:
-                        queue[j] = ObjectSample(rel_pts[i, inside[i]], box.copy(), conf=conf)
+                        queue[j] = ObjectSample(rel_pts(i), box.copy(), conf=conf)
             else:
-                queue.append(ObjectSample(rel_pts[i, inside[i]], box.copy(), conf=conf))
+                queue.append(ObjectSample(rel_pts(i), box.copy(), conf=conf))
         n_valid = len(valid_idx)
         out = np.zeros((num_proposals, 8))
         out[:n_valid] = pseudo_boxes[valid_idx]
@@ -367,8 +417,10 @@ class PseudoLoader(object):
         batch_dict['pseudo_samples_mask'] = np.zeros((len(boxes),), dtype=bool)
         return batch_dict
 
-    def copy_and_paste(self, batch_dict):
-        boxes, mask = self.sampler(batch_dict, self.copy_boxes, self.copy_scores, batch_dict['gt_boxes'], fix_cp=self.fix_cp)
+    def copy_and_paste(self, batch_dict, cut=None):
+        """cut: gt_sampling's pending cut (PseudoSampler.__call__), None in the reference's order of work"""
+        boxes, mask = self.sampler(batch_dict, self.copy_boxes, self.copy_scores, batch_dict['gt_boxes'], fix_cp=self.fix_cp,
+                                   cut=cut)
         boxes, non_empty = remove_empty(boxes)
         mask = mask[non_empty]
         if self.copy_st_only:                   # the frustum pseudos were kept out of the sampler: add them back

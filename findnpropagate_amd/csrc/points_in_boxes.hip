@@ -194,3 +194,83 @@ extern "C" int fnp_host_points_in_boxes_frame(const float *points, int n, int C,
     }
     return FNP_OK;
 }
+
+// ---- host entry point: the compact form of the same membership (PseudoSampler.__call__ feeding its queue) ----
+// Only the rows inside each box, box after box in row order: their count, their index and their box-frame row, each the
+// matching entry of fnp_host_points_in_boxes_frame (same expressions, same bits), without the (T, N) matrix.  Per box, a
+// vectorisable pass flags the rows with |x - cx| <= R and |y - cy| <= R, R = 1.001 * (|hx| + |hy|) + 1e-3; only flagged rows take
+// the exact test.  The prefilter drops no row the test keeps: the test's f32 rotation of (px, py) (two products and a sum,
+// relative error < 2^-22 of |px| + |py|; cos^2 + sin^2 within 2^-22 of 1) bounds max(|px|, |py|) <= |(px, py)| <
+// (|hx| + |hy|) * (1 + 1e-6) for a row inside, faces included.  A NaN fails both.
+// The pending cut: a row i with cut_from <= i < cut_to that lies inside one of the cut records (boxcut.h, the test the device cut
+// makes) is left out, as if the host had cut the scene first.  Each such row is tested against the records once.
+#include <cstring>
+#include <vector>
+
+#include "boxcut.h"
+
+extern "C" int fnp_host_points_in_boxes_compact(const float *points, int64_t n, int C, const float *boxes, int t,
+                                                const float *cut_records, int cut_m, int64_t cut_from, int64_t cut_to,
+                                                int *counts, int64_t capacity, int *indices, float *rows) {
+    if (n < 0 || n > 0x7fffffffll || t < 0 || C < 3 || cut_m < 0 || capacity < 0) return FNP_ERR_ARG;
+    if ((t > 0 && !counts) || (n > 0 && t > 0 && (!points || !boxes)) || (capacity > 0 && (!indices || !rows))) return FNP_ERR_ARG;
+    if (cut_m > 0 && !cut_records) return FNP_ERR_ARG;
+    const int N = (int)n;
+    std::vector<float> xs((size_t)N), ys((size_t)N);
+    for (int i = 0; i < N; ++i) {
+        xs[i] = points[(size_t)i * C];
+        ys[i] = points[(size_t)i * C + 1];
+    }
+    std::vector<unsigned char> flag((size_t)N + 8, 0);
+    std::vector<FnpCutBox> cb((size_t)cut_m);
+    for (int j = 0; j < cut_m; ++j) cb[j] = fnp_cut_box(cut_records + (size_t)j * 8);
+    std::vector<unsigned char> cut_state(cut_m > 0 ? (size_t)N : 0, 0);   // 0 untested, 1 kept, 2 cut
+    const int64_t lo = cut_from < 0 ? 0 : cut_from, hi = cut_to;
+    int64_t total = 0;
+    for (int b = 0; b < t; ++b) {
+        const float *bx = boxes + (size_t)b * 7;
+        const float ca = cosf(-bx[6]), sa = sinf(-bx[6]);
+        const float hx = bx[3] * 0.5f, hy = bx[4] * 0.5f, hz = bx[5] * 0.5f;
+        const float x1 = fminf(hx, -hx), x2 = fmaxf(hx, -hx), y1 = fminf(hy, -hy), y2 = fmaxf(hy, -hy);
+        const float z1 = fminf(hz, -hz), z2 = fmaxf(hz, -hz);
+        const float reach = (float)(1.001 * ((double)fabsf(hx) + (double)fabsf(hy)) + 1e-3);
+        const float cx = bx[0], cy = bx[1];
+        const float *__restrict__ px_ = xs.data();
+        const float *__restrict__ py_ = ys.data();
+        unsigned char *__restrict__ f = flag.data();
+        for (int i = 0; i < N; ++i) f[i] = (fabsf(px_[i] - cx) <= reach) & (fabsf(py_[i] - cy) <= reach);
+        int cnt = 0;
+        for (int i0 = 0; i0 < N; i0 += 8) {
+            uint64_t word;
+            memcpy(&word, f + i0, 8);
+            if (!word) continue;
+            const int i1 = i0 + 8 < N ? i0 + 8 : N;
+            for (int i = i0; i < i1; ++i) {
+                if (!f[i]) continue;
+                const float *p = points + (size_t)i * C;
+                const float px = p[0] - bx[0], py = p[1] - bx[1], pz = p[2] - bx[2];
+                const float rx = px * ca + py * (-sa), ry = px * sa + py * ca;
+                if (!(rx >= x1 && rx <= x2 && ry >= y1 && ry <= y2 && pz >= z1 && pz <= z2)) continue;
+                if (cut_m > 0 && i >= lo && i < hi) {
+                    if (!cut_state[i]) {
+                        bool in = false;
+                        for (int j = 0; j < cut_m && !in; ++j) in = fnp_cut_inside(cb[j], p[0], p[1], p[2]);
+                        cut_state[i] = in ? 2 : 1;
+                    }
+                    if (cut_state[i] == 2) continue;
+                }
+                const int64_t k = total + cnt;
+                if (k < capacity) {
+                    indices[k] = i;
+                    float *o = rows + (size_t)k * C;
+                    o[0] = rx; o[1] = ry; o[2] = pz;
+                    for (int c = 3; c < C; ++c) o[c] = p[c];
+                }
+                ++cnt;
+            }
+        }
+        counts[b] = cnt;
+        total += cnt;
+    }
+    return total > capacity ? FNP_ERR_WORKSPACE : FNP_OK;
+}

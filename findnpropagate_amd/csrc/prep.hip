@@ -20,8 +20,11 @@
 // fnp_prepare_points_cut adds gt_sampling's cut (DataBaseSampler.add_sampled_boxes_to_scene, database_sampler.py:367-452) to
 // the mark: row i of scene b is dropped when i >= off[b] + cut_from[b] (the pasted object rows lead the scene and are never cut)
 // and the row, before its program moves it, lies inside one of the scene's records [cut_offsets[b], cut_offsets[b+1]) (boxcut.h).
-// The two entry points share every kernel; the cut is a compile-time flag of the mark, and the no-cut instantiation is the
-// mark as it was.
+// fnp_prepare_points_cut_window also bounds the test from above: only rows with cut_from[b] <= i - off[b] < cut_to[b] are tested
+// (unknowns_copy_paste appends its pasted rows behind the scene rows, and the cut must not reach them).  The relative index is
+// compared, so a "to the end" cut_to such as INT32_MAX cannot overflow.
+// The entry points share every kernel; the cut is a compile-time flag of the mark, and the no-cut instantiation is the mark as
+// it was.  The window is a pointer of the cut (NULL: no upper bound).
 #include <vector>
 
 #include "boxcut.h"
@@ -136,12 +139,14 @@ struct CutArgs {
     const float *rec;   // (M, 8) records, boxcut.h
     const int *off;     // (B+1) scene b owns records [off[b], off[b+1])
     const int *from;    // (B)   scene b's rows [0, from[b]) are never cut
+    const int *to;      // (B)   or NULL: scene b's rows [to[b], end) are never cut either
 };
 
 // Is row i (raw x, y, z) of scene b cut?  A wave whose live lanes lie in one scene walks that scene's records with wave-uniform
 // loads and leaves the walk once no lane needs another box; a wave that straddles two scenes walks each lane's own records.
 __device__ __forceinline__ bool cut_row(const CutArgs &cut, const int *__restrict__ off, int b, int i, float x, float y, float z) {
-    const bool test = i >= off[b] + cut.from[b];
+    const int rel = i - off[b];
+    const bool test = rel >= cut.from[b] && (!cut.to || rel < cut.to[b]);
     bool inside = false;
     const int b0 = __builtin_amdgcn_readfirstlane(b);
     if (__ballot(b != b0) == 0) {
@@ -361,8 +366,20 @@ extern "C" int fnp_prepare_points_cut(const float *points, int64_t n_points, int
                                       int shuffle_mode, const int *perm, int64_t n_perm, uint64_t seed, float pad,
                                       void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream) {
     return prepare_points<true>(points, n_points, num_features, batch_offsets, batch_size, program, program_steps,
-                                CutArgs{cut_records, cut_offsets, cut_from}, x_min, y_min, x_max, y_max, shuffle_mode, perm, n_perm,
-                                seed, pad, workspace, workspace_bytes, out_points, out_offsets, stream);
+                                CutArgs{cut_records, cut_offsets, cut_from, nullptr}, x_min, y_min, x_max, y_max, shuffle_mode, perm,
+                                n_perm, seed, pad, workspace, workspace_bytes, out_points, out_offsets, stream);
+}
+
+extern "C" int fnp_prepare_points_cut_window(const float *points, int64_t n_points, int num_features, const int *batch_offsets,
+                                             int batch_size, const float *program, int program_steps, const float *cut_records,
+                                             const int *cut_offsets, const int *cut_from, const int *cut_to, double x_min,
+                                             double y_min, double x_max, double y_max, int shuffle_mode, const int *perm,
+                                             int64_t n_perm, uint64_t seed, float pad, void *workspace, int64_t workspace_bytes,
+                                             float *out_points, int *out_offsets, fnp_stream_t stream) {
+    if (!cut_to) return FNP_ERR_ARG;
+    return prepare_points<true>(points, n_points, num_features, batch_offsets, batch_size, program, program_steps,
+                                CutArgs{cut_records, cut_offsets, cut_from, cut_to}, x_min, y_min, x_max, y_max, shuffle_mode, perm,
+                                n_perm, seed, pad, workspace, workspace_bytes, out_points, out_offsets, stream);
 }
 
 // ---- host entry points of the cut (DataLoader workers: no device, no stream) ----

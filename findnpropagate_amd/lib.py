@@ -102,6 +102,7 @@ SIGNATURES = {
     "fnp_recall_counters": (c_int, [P, c_int, c_int, P, P, c_int, c_int, P, c_int, c_int, P, c_int, c_uint, c_uint, P, P]),
     "fnp_seeker_pack_records": (c_int, [P, P, P, c_int, P, c_int, c_int, P, P]),
     "fnp_host_points_in_boxes_frame": (c_int, [P, c_int, c_int, P, c_int, P, P]),
+    "fnp_host_points_in_boxes_compact": (c_int, [P, c_int64, c_int, P, c_int, P, c_int, c_int64, c_int64, P, c_int64, P, P]),
     "fnp_host_boxes_iou_bev": (c_int, [P, c_int, P, c_int, P]),
     "fnp_host_boxes_aligned_iou_bev": (c_int, [P, P, c_int, P]),
     "fnp_nms_workspace_bytes": (c_int64, [c_int]),
@@ -129,6 +130,8 @@ SIGNATURES = {
     "fnp_host_points_outside_boxes": (c_int, [P, c_int64, c_int, P, c_int, P]),
     "fnp_prepare_points_cut": (c_int, [P, c_int64, c_int, P, c_int, P, c_int, P, P, P, c_double, c_double, c_double, c_double,
                                        c_int, P, c_int64, c_uint64, c_float, P, c_int64, P, P, P]),
+    "fnp_prepare_points_cut_window": (c_int, [P, c_int64, c_int, P, c_int, P, c_int, P, P, P, P, c_double, c_double, c_double,
+                                              c_double, c_int, P, c_int64, c_uint64, c_float, P, c_int64, P, P, P]),
     "fnp_rulebook_subm": (c_int, [P, P, c_int, POINTER(ConvGeom), POINTER(RankGridC), P, P]),
     "fnp_rulebook_strided": (c_int, [P, P, c_int, POINTER(ConvGeom), POINTER(RankGridC), POINTER(RankGridC),
                                      P, P, c_int, P, P, c_int64, P]),

@@ -211,7 +211,9 @@ def prepare_points(points, batch_offsets, batch_size, program, point_cloud_range
     cut: gt_sampling's cut (fnp_prepare_points_cut), or None.  (records (M, 8) f32, box_offsets (B+1,) int32, cut_from (B,) int32),
     device tensors (augmentor.data_augmentor.stack_cut_boxes of what DataAugmentor records in deferred mode): row i of scene b is
     dropped when i >= batch_offsets[b] + cut_from[b] and the raw row lies inside one of records[box_offsets[b]:box_offsets[b+1]],
-    before the program moves it (the host mode's remove_points_in_boxes3d, bit for bit).
+    before the program moves it (the host mode's remove_points_in_boxes3d, bit for bit).  A 4-tuple (records, box_offsets,
+    cut_from, cut_to) adds cut_to (B,) int32 (fnp_prepare_points_cut_window): only rows with cut_from[b] <= i - batch_offsets[b]
+    < cut_to[b] are tested (unknowns_copy_paste's prep_cut_to: the pasted rows behind the scene rows are never cut).
 
     Returns dict(points (N,C) f32: the kept rows scene after scene, then PREP_PAD rows; batch_offsets (B+1,) int32: the new
     offsets; n (1,) int32: the kept count; batch_size) — points and batch_offsets are what voxelize / forward_points take, over
@@ -258,15 +260,21 @@ def prepare_points(points, batch_offsets, batch_size, program, point_cloud_range
                                   _l.ptr(program) if K else None, K, *tail)
         _l.check(rc, "fnp_prepare_points")
         return out
-    records, box_off, cut_from = cut
+    records, box_off, cut_from = cut[:3]
     _l.require_device(records, box_off, cut_from)
     assert records.dtype == torch.float32 and records.dim() == 2 and records.shape[1] == 8 and records.is_contiguous()
     assert box_off.dtype == torch.int32 and box_off.numel() == batch_size + 1 and box_off.is_contiguous()
     assert cut_from.dtype == torch.int32 and cut_from.numel() == batch_size and cut_from.is_contiguous()
-    rc = L.fnp_prepare_points_cut(_l.ptr(points) if n else None, n, C, _l.ptr(batch_offsets), batch_size,
-                                  _l.ptr(program) if K else None, K,
-                                  _l.ptr(records) if records.numel() else None, _l.ptr(box_off), _l.ptr(cut_from), *tail)
-    _l.check(rc, "fnp_prepare_points_cut")
+    head = (_l.ptr(points) if n else None, n, C, _l.ptr(batch_offsets), batch_size, _l.ptr(program) if K else None, K,
+            _l.ptr(records) if records.numel() else None, _l.ptr(box_off), _l.ptr(cut_from))
+    if len(cut) == 3:
+        _l.check(L.fnp_prepare_points_cut(*head, *tail), "fnp_prepare_points_cut")
+        return out
+    assert len(cut) == 4, "cut: (records, box_offsets, cut_from) or (records, box_offsets, cut_from, cut_to)"
+    cut_to = cut[3]
+    _l.require_device(cut_to)
+    assert cut_to.dtype == torch.int32 and cut_to.numel() == batch_size and cut_to.is_contiguous()
+    _l.check(L.fnp_prepare_points_cut_window(*head, _l.ptr(cut_to), *tail), "fnp_prepare_points_cut_window")
     return out
 
 

@@ -106,6 +106,17 @@ int fnp_recall_counters(const float *preds, int pred_stride, int max_preds, cons
 int fnp_host_points_in_boxes_frame(const float *points, int n, int C, const float *boxes, int t,
                                    unsigned char *in_box, float *points_out);
 
+/* The same membership in compact form (no (T, N) matrix): counts (T,) int32, the rows inside box t; box after box, in row order,
+ * the row indices (int32) and the box-frame rows (C f32 each) of those rows: the entries of fnp_host_points_in_boxes_frame's
+ * in_box and points_out, bit for bit.  indices (capacity,) and rows (capacity, C) receive the first `capacity` of them; counts
+ * are always complete, and the call returns FNP_ERR_WORKSPACE when their sum exceeds capacity (call again with that size).
+ * The pending cut (cut_m == 0: none): rows i with cut_from <= i < cut_to that lie inside one of the cut_m records
+ * (fnp_host_cut_records; the test of fnp_host_points_outside_boxes and the device cut) are left out; indices still number the
+ * input rows.  n < 2^31.  Host pointers, no device. */
+int fnp_host_points_in_boxes_compact(const float *points, int64_t n, int C, const float *boxes, int t,
+                                     const float *cut_records, int cut_m, int64_t cut_from, int64_t cut_to,
+                                     int *counts, int64_t capacity, int *indices, float *rows);
+
 /* Host-side rotated BEV IoU (no device, no stream): replaces boxes_iou_bev_cpu (N x M) and
  * boxes_aligned_iou_bev_cpu (N pairs) of pcdet/ops/iou3d_nms/src/iou3d_cpu.cpp:232-272, called by the
  * pseudo-label mixing in dataloader workers (pseudo_loader.py:29-55).  Host pointers, (n,7) boxes. */
@@ -274,6 +285,15 @@ int fnp_prepare_points_cut(const float *points, int64_t n_points, int num_featur
                            const int *cut_from, double x_min, double y_min, double x_max, double y_max,
                            int shuffle_mode, const int *perm, int64_t n_perm, uint64_t seed, float pad,
                            void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream);
+
+/* fnp_prepare_points_cut with a window: row i of scene b is tested against the scene's records only when
+ * cut_from[b] <= i - off[b] < cut_to[b] (cut_to (B,) int32 device, not NULL; INT32_MAX: to the end of the scene), so rows that
+ * unknowns_copy_paste appended behind the scene rows are never cut.  Everything else as fnp_prepare_points_cut. */
+int fnp_prepare_points_cut_window(const float *points, int64_t n_points, int num_features, const int *batch_offsets, int batch_size,
+                                  const float *program, int program_steps, const float *cut_records, const int *cut_offsets,
+                                  const int *cut_from, const int *cut_to, double x_min, double y_min, double x_max, double y_max,
+                                  int shuffle_mode, const int *perm, int64_t n_perm, uint64_t seed, float pad,
+                                  void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Rulebooks — replace spconv's indice-pair generation for SubMConv3d / SparseConv3d

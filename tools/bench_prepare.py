@@ -5,12 +5,16 @@ device: sparse.prepare_points (fnp_prepare_points, device shuffle and explicit-p
         launches, for B = 4 ten-sweep scenes (~300 k points each) and B = 128 single-sweep scenes (~30 k points each);
         with gt_sampling's cut (fnp_prepare_points_cut, device shuffle) of 39 boxes per ten-sweep scene and 25 per single-sweep
         scene, the boxes centred on scene points with nuScenes class sizes (cut_us against no_cut_us, the same launch without it);
+        and the windowed cut (fnp_prepare_points_cut_window, cut_window_us) with every scene's cut_to 1000 rows short of its end;
 host:   the same work as the reference does it per scene in DataLoader workers (DataAugmentor host mode + mask_points_by_range +
         np.random.permutation), wall time per batch with 1 worker process and with 16, torch at one thread per process; and the
         host-mode cut (fnp_host_points_outside_boxes + the compaction) per scene, median, in one worker.
 Host timings run first, in forked workers, before this process touches the GPU.
+--membership: only the copy-paste queue's membership per frame on one core (no GPU): PseudoSampler's dense
+        points_in_boxes (fnp_host_points_in_boxes_frame, (T, N) mask + (T, N, 5) rows) against points_in_boxes_compact
+        (fnp_host_points_in_boxes_compact), 300 k uniform points x {10, 30, 60} random boxes, median ms.
 
-    python tools/bench_prepare.py [--reps 50]
+    python tools/bench_prepare.py [--reps 50] [--membership]
 """
 import argparse
 import json
@@ -114,9 +118,10 @@ def device_cut_time(scenes, boxes, reps):
     off = torch.from_numpy(np.concatenate([[0], np.cumsum([s.shape[0] for s in scenes])]).astype(np.int32)).to(dev)
     prog = torch.from_numpy(stack_programs(progs)).to(dev)
     cut = tuple(torch.from_numpy(a).to(dev) for a in stack_cut_boxes(boxes, [0] * len(scenes)))
+    window = tuple(torch.from_numpy(a).to(dev) for a in stack_cut_boxes(boxes, [0] * len(scenes), [s.shape[0] - 1000 for s in scenes]))
     B = len(scenes)
     res = {}
-    for name, c in (("no_cut", None), ("cut", cut)):
+    for name, c in (("no_cut", None), ("cut", cut), ("cut_window", window)):
         out = S.prepare_points(pts, off, B, prog, syn.POINT_CLOUD_RANGE, shuffle="device", cut=c)
         for _ in range(5):
             S.prepare_points(pts, off, B, prog, syn.POINT_CLOUD_RANGE, shuffle="device", cut=c, out=out)
@@ -170,11 +175,38 @@ def device_time(scenes, reps):
     return res
 
 
+def membership_time(reps=5):
+    from findnpropagate_amd.augmentor import pseudo_loader as PL
+
+    rng = np.random.default_rng(0)
+    pts = rng.uniform(-54, 54, (300000, 5)).astype(np.float32)
+    pts[:, 2] = rng.uniform(-5, 3, 300000)
+    out = {"metric": "queue_membership", "points": 300000}
+    for T in (10, 30, 60):
+        boxes = syn.random_boxes(rng, T, centre_range=50.0)
+        row = {}
+        for name, fn in (("dense_ms", lambda: PL.points_in_boxes(pts, boxes)),
+                         ("compact_ms", lambda: PL.points_in_boxes_compact(pts, boxes))):
+            ts = []
+            for _ in range(reps):
+                t0 = time.perf_counter()
+                fn()
+                ts.append((time.perf_counter() - t0) * 1e3)
+            row[name] = round(float(np.median(ts)), 2)
+        row["rows_kept"] = int(PL.points_in_boxes_compact(pts, boxes)[0].sum())
+        out[f"boxes_{T}"] = row
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--workers", type=int, default=16)
+    ap.add_argument("--membership", action="store_true")
     a = ap.parse_args()
+    if a.membership:
+        print(json.dumps(membership_time()))
+        return
     pts, off = syn.make_sweeps_batch([0, 1, 2, 3])
     sweeps = [pts[off[b]:off[b + 1]] for b in range(4)]
     pts, off = syn.make_batch(range(128))
