@@ -4,7 +4,7 @@
 The rulebooks, features and weights of the ranked 32 -> 32 and 64 -> 64 SubM stages of a B-scene forward are made once with the
 shipped library; every variant library (tools/build_variant.sh: findnpropagate_amd/csrc/ab/libfnp_<name>.so) is loaded with
 ctypes and launched on the SAME device buffers in interleaved rounds (box-to-box and run-to-run drift cancels), its output
-compared bit for bit with the shipped kernel's.  usage: tools/ab_tiled.py --batch 64 --variants s2,s3 [--channels 64,32]"""
+compared bit for bit with the shipped kernel's.  usage: tools/ab_tiled.py --batch 64 --variants s2,s3 [--channels 64,32] [--warm-rounds 2]"""
 import argparse, ctypes, json, os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
@@ -15,6 +15,8 @@ from findnpropagate_amd.backbones_3d import VoxelResBackBone8x
 ap = argparse.ArgumentParser()
 ap.add_argument("--batch", type=int, default=64); ap.add_argument("--variants", default=""); ap.add_argument("--channels", default="64,32")
 ap.add_argument("--rounds", type=int, default=5); ap.add_argument("--reps", type=int, default=20)
+ap.add_argument("--warm-rounds", type=int, default=0, help="untimed rounds of the same interleave before the timed ones (the first timed round otherwise "
+                "carries the clock ramp, and the library that runs first in a round carries most of it)")
 ap.add_argument("--plain128", action="store_true", help="channels 128: fnp_spconv_forward (row order) instead of the class-sorted sweep")
 args = ap.parse_args()
 dev = torch.device("cuda", 0)
@@ -81,7 +83,7 @@ for tag, rb, n_dev in log:
         torch.cuda.synchronize()
         equal = {name: bool(torch.equal(outs[name][:n], outs["main"][:n])) for name in libs}
         times = {name: [] for name in libs}
-        for _ in range(args.rounds):
+        for rnd in range(args.warm_rounds + args.rounds):
             for name in libs:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
@@ -89,7 +91,8 @@ for tag, rb, n_dev in log:
                     launch(name)
                 e1.record()
                 torch.cuda.synchronize()
-                times[name].append(e0.elapsed_time(e1) / args.reps)
+                if rnd >= args.warm_rounds:
+                    times[name].append(e0.elapsed_time(e1) / args.reps)
         print(json.dumps({"channels": cin, "kernel": "plain" if args.plain128 else "sorted", "rows": n, "scenes": B,
                           "ms_per_launch_median": {k: round(float(np.median(v)), 4) for k, v in times.items()},
                           "ms_all_rounds": {k: [round(t, 4) for t in v] for k, v in times.items()}, "bit_identical_to_main": equal}), flush=True)

@@ -29,6 +29,9 @@ def short(k):
     m = re.search(r'spconv_mfma_kernel<(\d+), (\d+), (\d+), (\d+), (true|false), (__bf16|float)>', k)
     if m:
         return "spconv_mfma_kernel<%s,%s,%s,%s,%s,%s>" % (*m.groups()[:5], "bf16" if m.group(6) == "__bf16" else "f32")
+    m = re.search(r'spconv_rows128_kernelI(DF16b|DF16_)E', k) or re.search(r'spconv_rows128_kernel<(__bf16|_Float16)>', k)
+    if m:   # (spconv_rows128.hip: the class-sorted 128 -> 128, 3x3x3 sweep as the LDS-DMA row pipeline)
+        return "spconv_rows128_kernel<%s>" % ("bf16" if m.group(1) in ("DF16b", "__bf16") else "f16")
     m = re.search(r'spconv_mfma_f32_kernelILi(\d+)ELi(\d+)ELi(\d+)ELb(\d)E', k)
     if m:
         return "spconv_mfma_f32_kernel<%s,%s,%s>" % (m.group(1), m.group(2), m.group(3))
