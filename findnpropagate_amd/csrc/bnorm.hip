@@ -17,14 +17,9 @@
 namespace {
 
 constexpr int kThreads = 256;
-#ifndef FNP_BN_PARTS
-#define FNP_BN_PARTS 256
-#endif
-constexpr int kMaxParts = FNP_BN_PARTS;   // statistics workgroups (one per CU; 1024 measured: the passes 7 % faster, the finishing launches
-                                          // 2.4x slower — 7.2 -> 17.5 us for 42 of them per step)
-#ifndef FNP_BN_UNROLL
-#define FNP_BN_UNROLL 4
-#endif
+constexpr int kMaxParts = 256;   // statistics workgroups (one per CU; 1024 measured: the passes 7 % faster, the finishing launches
+                                 // 2.4x slower — 7.2 -> 17.5 us for 42 of them per step)
+constexpr int kUnroll = 4;       // rows a statistics thread requests per trip
 constexpr int kFinC = 16;        // channels per finishing workgroup
 
 __device__ __forceinline__ float ldf(const float *p, size_t i) { return p[i]; }
@@ -68,13 +63,10 @@ template <typename T> __device__ __forceinline__ void store8(T *p, const float (
 // four stages at 16 scenes): 22.8 / 44.4 / 51.0 / 44.0 -> 21.5 / 39.5 / 43.2 / 38.4 us forward, 29.5 / 62.4 / 71.1 / 60.8 -> 27.1 /
 // 55.8 / 63.0 / 54.0 us backward, every output bit-identical (1,024 threads: the 16-channel stage slower than before, the rest
 // as 512).
-#ifndef FNP_BN_STAT_THREADS
-#define FNP_BN_STAT_THREADS 512
-#endif
-constexpr int kStatThreads = FNP_BN_STAT_THREADS;
+constexpr int kStatThreads = 512;
 // whole waves; 32 lanes per row at most (C <= 256) must fit a wave-aligned workgroup; red[NW][32][16] f64 is 4 KB per wave of
 // static LDS: 1,024 threads sit exactly on the 64 KB limit
-static_assert(kStatThreads % 64 == 0 && kStatThreads >= 64 && kStatThreads <= 1024, "FNP_BN_STAT_THREADS: a multiple of 64 in [64, 1024]");
+static_assert(kStatThreads % 64 == 0 && kStatThreads >= 64 && kStatThreads <= 1024, "kStatThreads: a multiple of 64 in [64, 1024]");
 __device__ __forceinline__ double shfl_xor_f64(double v, int m) {
     int lo = __double2loint(v), hi = __double2hiint(v);
     lo = __shfl_xor(lo, m);
@@ -108,7 +100,7 @@ __global__ __launch_bounds__(kStatThreads) void bn_stats_kernel(const T *__restr
     const long long per = ((long long)n + gridDim.x - 1) / gridDim.x;
     const long long r0 = per * blockIdx.x, r1 = min((long long)n, r0 + per);
     // U rows per trip: their loads (U, 2 U or 3 U of 16 bytes) are all requested before the first is used; the sums stay in row order
-    constexpr int U = MODE == 1 ? (FNP_BN_UNROLL + 1) / 2 : FNP_BN_UNROLL;   // (backward: three tensors per row, 128 registers at 16 waves per CU)
+    constexpr int U = MODE == 1 ? (kUnroll + 1) / 2 : kUnroll;   // (backward: three tensors per row, 128 registers at 16 waves per CU)
     for (long long r = r0 + rl; r < r1; r += (long long)U * rows_per_iter) {
         float xv[U][8], gv[U][8], yv[U][8];
 #pragma unroll
@@ -164,8 +156,8 @@ __global__ __launch_bounds__(kStatThreads) void bn_stats_kernel(const T *__restr
     }
     __syncthreads();
     // slot (channel group g, sum j of 16) adds the waves' lines in wave order; a strided loop over the tpr * 16 <= 512 slots, so that
-    // any workgroup size of the FNP_BN_STAT_THREADS switch writes every partial (with `threadIdx.x < tpr * 16` a
-    // 256-thread build left the partials of channel groups 16-31 of a 256-channel layer unwritten)
+    // any kStatThreads writes every partial (with `threadIdx.x < tpr * 16` a 256-thread build left the partials of
+    // channel groups 16-31 of a 256-channel layer unwritten)
     for (int slot = threadIdx.x; slot < tpr * 16; slot += kStatThreads) {
         const int g = slot >> 4, j = slot & 15;
         double v = 0.0;

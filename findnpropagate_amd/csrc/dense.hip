@@ -151,9 +151,7 @@ __global__ __launch_bounds__(kThreads) void dense_write_kernel(const T *__restri
 // Cells per lane.  Measured on MI355X (16 scenes, 265 MB bf16): 2 -> 101 us (2.6 TB/s), 4 -> 120 us,
 // 8 -> 296 us (tiles of 256+ cells overflow the 64 LDS slots near the ego vehicle and take the element-
 // store path), 1 -> 134 us; memset + row scatter 264 us.
-#ifndef FNP_DENSE_VEC
-#define FNP_DENSE_VEC 2
-#endif
+constexpr int kDenseVec = 2;
 
 template <typename T, int VEC>
 int launch_dense_write(const void *feats, const int *index, int C, int B, int D, long long plane, void *out, const float *fill, hipStream_t s) {
@@ -201,7 +199,7 @@ int run_dense(const void *feats, const int *coords, const int *n_rows, int cap, 
     FNP_LAUNCH_CHECK();
     // widest store (<= 16 bytes per lane) that the plane size and the buffer alignment allow
     const bool al = ((uintptr_t)out % 16 == 0) && ((uintptr_t)ws % 16 == 0);
-    constexpr int kMaxVec = 16 / (int)sizeof(T) < FNP_DENSE_VEC ? 16 / (int)sizeof(T) : FNP_DENSE_VEC;
+    constexpr int kMaxVec = 16 / (int)sizeof(T) < kDenseVec ? 16 / (int)sizeof(T) : kDenseVec;
     if constexpr (kMaxVec >= 8) {
         if (al && plane % 8 == 0) return launch_dense_write<T, 8>(feats, index, C, B, D, plane, out, fill, s);
     }
@@ -389,7 +387,7 @@ int run_dense_backward(const void *grad_out, const int *coords, const int *n_row
                        n_rows, cap, C, B, D, H, W, index, (T *)grad_feats);
     FNP_LAUNCH_CHECK();
     const bool al = ((uintptr_t)grad_out % 16 == 0) && ((uintptr_t)ws % 16 == 0);
-    constexpr int kMaxVec = 16 / (int)sizeof(T) < FNP_DENSE_VEC ? 16 / (int)sizeof(T) : FNP_DENSE_VEC;
+    constexpr int kMaxVec = 16 / (int)sizeof(T) < kDenseVec ? 16 / (int)sizeof(T) : kDenseVec;
     if constexpr (kMaxVec >= 8) {
         if (al && plane % 8 == 0) return launch_dense_grad<T, 8>(grad_out, index, C, B, D, plane, grad_feats, s);
     }

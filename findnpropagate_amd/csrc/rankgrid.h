@@ -81,10 +81,6 @@ inline RG fnp_rg_view(const fnp_rankgrid *g) {
     r.nsum = (r.nblk + 63) >> 6;
     r.ctr = (unsigned *)g->counters;
     r.wpw = fnp_rg_wpw(r.nsum);
-    {   // development: FNP_WPW_BIG=8 / 16 / 64 — the unit size of the large grids
-        static const int big = [] { const char *e = getenv("FNP_WPW_BIG"); return e ? atoi(e) : 0; }();
-        if (big > 0 && r.wpw == 16) r.wpw = big;
-    }
     r.nunits = (r.nsum + r.wpw - 1) / r.wpw;
     r.ctr_levels = fnp_count_levels();
     return r;
@@ -166,9 +162,6 @@ struct MarkTab {
     unsigned long long val[kMarkTab];
     CntTab cnt;                         // new cells per unit (counted marks, below mark_tab_flush)
 };
-#ifndef FNP_MARK_TAB
-#define FNP_MARK_TAB 1
-#endif
 __device__ __forceinline__ void rg_count_put(MarkTab *tab, const RG &g, long long blk, int inc) {
     if (!g.ctr || inc <= 0) return;
     const unsigned U = (unsigned)((blk >> 6) / g.wpw);
@@ -184,7 +177,7 @@ __device__ __forceinline__ void rg_count_put(MarkTab *tab, const RG &g, long lon
     rg_count_global(g, U, (unsigned)inc);   // (a crowded table: straight to memory)
 }
 __device__ __forceinline__ void mark_put(MarkTab *tab, const RG &go, long long blk, unsigned long long m) {
-    if (!FNP_MARK_TAB || !tab) {
+    if (!tab) {   // (the marks a rulebook kernel makes on the side: straight to memory)
         const int inc = rg_mark_mask(go, blk, m);
         if (go.ctr && inc > 0) rg_count_global(go, (unsigned)((blk >> 6) / go.wpw), (unsigned)inc);
         return;

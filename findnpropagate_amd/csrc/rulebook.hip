@@ -15,6 +15,10 @@
 #include "rankgrid.h"
 #include "tilerb.h"
 
+// Instrument (development builds only; the shipped library leaves it undefined):
+//   FNP_RBT_ABLATE  timing probes of the SubM kernel's tile-rulebook output, a bit mask (its entries are wrong): 1 = the entries
+//                   are the raw row ids (no window / far-row lookup), 2 = the entries are not stored
+
 namespace {
 
 constexpr int kThreads = 256;
@@ -182,7 +186,7 @@ __global__ __launch_bounds__(kThreads) void strided_mark2_kernel(const int *__re
     const int lane = fnp_lane();
     const int span = order ? cap_in : n;   // ranks of dropped / absent cells map to -1
     const int nround = (span + (int)(gridDim.x * kThreads) - 1) / (int)(gridDim.x * kThreads);
-    if (FNP_MARK_TAB) mark_tab_init(&tab, threadIdx.x, kThreads);
+    mark_tab_init(&tab, threadIdx.x, kThreads);
     // the row id and coordinates of the NEXT round are requested before this round's dependent chain
     // (occupancy-word read -> atomic -> summary atomic) is walked: two of its five memory round trips overlap
     auto fetch = [&](int it, int &row, int4 &c) {
@@ -200,8 +204,8 @@ __global__ __launch_bounds__(kThreads) void strided_mark2_kernel(const int *__re
         const int row = row_n;
         const int4 c = c_n;
         fetch(it + 1, row_n, c_n);
-        mark2_row<SZ, SY, SX>(row >= 0, c, go, ge, lane, FNP_MARK_TAB ? &tab : nullptr);
-        if (FNP_MARK_TAB) mark_tab_flush(&tab, go, threadIdx.x, kThreads);   // (the passes of a workgroup lie far apart: nothing to merge across them)
+        mark2_row<SZ, SY, SX>(row >= 0, c, go, ge, lane, &tab);
+        mark_tab_flush(&tab, go, threadIdx.x, kThreads);   // (the passes of a workgroup lie far apart: nothing to merge across them)
     }
 }
 

@@ -4,7 +4,6 @@
 // blocks are read.
 #include "rankgrid.h"
 #include <cstdint>
-#include <cstdlib>
 #include <type_traits>
 
 namespace {
@@ -153,8 +152,7 @@ int run_scan(L load, long long n, TOut *out, int *total, void *ws, hipStream_t s
     if (!out || !ws) return FNP_ERR_ARG;
     const int tiles = fnp_divup(n, fnp_scan::kTile);
     if constexpr (std::is_same<L, LoadInt>::value && std::is_same<TOut, int>::value) {
-        static const bool small_ok = [] { const char *e = getenv("FNP_SMALL_SCAN"); return !e || atoi(e) != 0; }();   // (development switch)
-        if (small_ok && tiles <= kSmallTiles && (const int *)out != load.p && (((uintptr_t)load.p | (uintptr_t)out) & 15) == 0) {   // (not in place: a workgroup reads the tiles in front of its own)
+        if (tiles <= kSmallTiles && (const int *)out != load.p && (((uintptr_t)load.p | (uintptr_t)out) & 15) == 0) {   // (not in place: a workgroup reads the tiles in front of its own)
             hipLaunchKernelGGL(small_scan_kernel, dim3(tiles), dim3(kThreads), 0, s, load.p, (int)n, out, total);
             FNP_LAUNCH_CHECK();
             return FNP_OK;

@@ -74,7 +74,7 @@ __device__ __forceinline__ int fnp_tail_blocks(int rows_left, int S, int NW) {
     return ((nb + S - 1) / S + NW - 1) / NW;
 }
 
-// tile of the class-sorted 16-bit sweep: 8 waves x 3 blocks x 16 positions (MfmaWg<128, 128>::NW, FNP_MB128 of spconv.hip)
+// tile of the class-sorted 16-bit sweep: 8 waves x 3 blocks x 16 positions (MfmaWg<128, 128>::NW and ::MB of spconv.hip)
 constexpr int kSortedNW = 8, kSortedMB = 3;
 
 }  // namespace

@@ -21,7 +21,18 @@
 #include "rankgrid.h"
 #include "sortedsweep.h"   // Vec16, mfma16, SortedRb, the sorted work split
 #include <type_traits>
-#include <cstdlib>
+
+// Instruments (development builds only, tools/bench_conv.py with FNP_LIB_PATH; the shipped library has neither):
+//   FNP_ABLATE      timing probes, a bit mask (results are wrong): 1 = no feature gathers, 2 = no weight staging, 4 = no MFMA,
+//                   8 = window kernels issue no global gathers, 16 = no window reads, 32 = rulebook entries read from a 64 KiB
+//                   (cache-resident) slice of the table, 64 = window address taken from the entry without arithmetic (timing
+//                   probe for pre-computed addresses), 128 = no output stores, 256 = no residual loads, 512 = no rulebook loads
+//                   (every neighbour row + k - 13 present)
+//   FNP_MFMA_STAMP  phase clocks of the 128 -> 128 sweep: s_memtime ticks per phase, summed over waves; fnp_debug_mfma_stamps()
+//                   returns and clears them
+#ifndef FNP_ABLATE
+#define FNP_ABLATE 0
+#endif
 
 namespace {
 
@@ -142,7 +153,7 @@ int launch_first(const void *x, const void *w, const int *nbr, int nbr_stride, i
 // ------------------------------------------------------------------------------------------
 // MFMA path.
 //
-// Workgroup = NW waves (4; 8 for 128 -> 128 channels); wave w owns MB*16 output sites and all COUT
+// Workgroup = NW waves (MfmaWg); wave w owns MB*16 output sites and all COUT
 // channels, accumulators in registers for the whole sweep over the K kernel offsets.  The weight slab
 // W_k (COUT x CIN bf16) is shared by the waves through LDS:
 //   * ALLK  (K*slab <= 64 KiB: the 16/32-channel layers): every slab is staged once per
@@ -170,106 +181,46 @@ struct MfmaCfg {
     // of gather instructions (15.6 clk per 64-lane b128 instruction per CU, whether or not its lanes are in
     // range): lanes q < 2 take offset 2p, lanes q >= 2 offset 2p + 1, the weight image holds [W_2p | W_2p+1]
     // per output channel, and the sweep has 14 steps instead of 27.
-#ifndef FNP_PAIR16
-#define FNP_PAIR16 1
-#endif
-    static constexpr bool PAIR = FNP_PAIR16 && CIN == 16 && KVOL == 27;
+    static constexpr bool PAIR = CIN == 16 && KVOL == 27;
     static constexpr int KEFF = PAIR ? (KVOL + 1) / 2 : KVOL;   // steps of the offset sweep
     static constexpr int CH = PAIR ? 4 : CIN / 8;         // 16-byte chunks per weight row (image row)
     static constexpr int SLAB = COUT * CH;                // chunks per slab
     static constexpr int SW = (CH == 8 || CH == 4) ? 1 : 0;
     static constexpr bool ALLK = KVOL > 0 && (long long)KEFF * SLAB * 16 <= 65536;
-    // WPAIR (128 -> 128, 8-wave workgroups): a ring of four slab buffers and ONE barrier per two offsets
-#ifndef FNP_WPAIR
-#define FNP_WPAIR 0
-#endif
-    static constexpr bool WPAIR = FNP_WPAIR && !ALLK && CIN == 128 && COUT == 128;
-    static constexpr int LDS_BYTES = (ALLK ? KEFF : WPAIR ? 4 : 2) * SLAB * 16;
+    static constexpr int LDS_BYTES = (ALLK ? KEFF : 2) * SLAB * 16;
     static constexpr int KS = (CIN + 31) / 32;            // 32-wide K steps of the MFMA
     // gather prefetch distance in kernel offsets: 16 gathers in flight per wave
-#ifndef FNP_PFK128
-#define FNP_PFK128 1   // (probe, round 5: fragments of the 128 -> 128 sweep requested TWO offsets ahead)
-#endif
-    static constexpr int PFK = ALLK ? (KS == 1 ? 4 : 2) : (CIN == 128 && COUT == 128 && KVOL == 27) ? FNP_PFK128 : 1;
-    // feature window (WIN kernels, 32/64-channel layers): rows [tile - WH, tile + rows + WH) of the
+    static constexpr int PFK = ALLK ? (KS == 1 ? 4 : 2) : 1;
+    // feature window (WIN kernel, the 64 -> 64 layers): rows [tile - WH, tile + rows + WH) of the
     // input tensor are staged in LDS once per tile; WZERO bytes of zeros follow them
-#ifndef FNP_WH32
-#define FNP_WH32 64
-#endif
-    static constexpr int WH = CH == 4 ? FNP_WH32 : 64;
+    static constexpr int WH = 64;
     static constexpr int WZERO = 128;
-    static constexpr int XLB = KS == 1 ? 2 : 1;           // window fragments are read XLB offsets ahead
     static constexpr int win_rows(int nw, int mb) { return nw * mb * 16 + 2 * WH; }
     // wide epilogue (bf16 outputs, >= 32 channels): one 16-site block of the wave's tile is transposed through a
     // wave-private LDS strip so that residual reads and output stores move 16 bytes per lane over whole rows
     // (128-byte cache lines) instead of 8 bytes per lane over 32-byte row pieces.
-#ifndef FNP_WIDE_EPI
-#define FNP_WIDE_EPI 1
-#endif
-    static constexpr bool WIDE = FNP_WIDE_EPI && COUT >= 32 && !WPAIR;   // (WPAIR: no LDS left for the strips -> swap form)
+    static constexpr bool WIDE = COUT >= 32;
     static constexpr int ESTRIDE = COUT * 2 + 16;   // bytes per staged row
-#ifndef FNP_EPI_SITES
-#define FNP_EPI_SITES 16
-#endif
-    static constexpr int epi_sites(bool win) { return win ? 8 : (COUT >= 128 ? FNP_EPI_SITES : 16); }   // sites per strip pass (window kernels: LDS is tight)
+    static constexpr int epi_sites(bool win) { return win ? 8 : 16; }   // sites per strip pass (window kernels: LDS is tight)
     static constexpr int epi_bytes(int nw, bool win, bool out16) { return (WIDE && out16 && !win) ? nw * epi_sites(win) * ESTRIDE : 0; }
     static constexpr int lds_bytes(int nw, int mb, bool win) { return LDS_BYTES + (win ? win_rows(nw, mb) * CH * 16 + WZERO : 0); }
 };
 
-// Development-only ablation bit mask (tools/bench_conv.py with FNP_LIB_PATH): 1 = no feature gathers,
-// 2 = no weight staging, 4 = no MFMA, 8 = window kernels issue no global gathers, 16 = no window reads,
-// 32 = rulebook entries read from a 64 KiB (cache-resident) slice of the table, 64 = window address taken
-// from the entry without arithmetic (timing probe for pre-computed addresses), 128 = no output stores,
-// 256 = no residual loads, 512 = no rulebook loads (every neighbour row + k - 13 present).  The shipped library is built with FNP_ABLATE == 0.
-#ifndef FNP_ABLATE
-#define FNP_ABLATE 0
-#endif
-#ifndef FNP_NT_STORE
-#define FNP_NT_STORE 0   // (development: output rows stored with the non-temporal hint — measured within the noise of a box, round 4)
-#endif
-// L2 line-touch prefetch of the rows above a tile (bit 0) — see run_tile
-#ifndef FNP_PF
-#define FNP_PF 0
-#endif
-// window kernel epilogue: 16-byte accesses through lane-row swaps (see the epilogue)
-#ifndef FNP_SWAP_EPI
-#define FNP_SWAP_EPI 1
-#endif
+template <int CIN, int COUT> struct MfmaWg {
+    // waves per workgroup: 8 for the 32/64/128-channel SubM layers (128 -> 128: one 32 KiB weight slab per offset then
+    // serves 384 sites instead of 192: the slab stream through L2 is the largest term of those layers), 4 elsewhere
+    static constexpr int NW = (CIN == COUT && CIN >= 32) ? 8 : 4;
+    // 16-site blocks per wave: 4 (64 sites); 3 for 128 output channels (accumulators = COUT/16 * MB * 4 registers:
+    // 3 measured 13 % faster than 2, 4 spills heavily); 2 for the other SubM layers and 16 -> 32 (8 % of the pairs
+    // present: 2 blocks at 4 waves/SIMD measured 9 % faster than 4 blocks at 3)
+    static constexpr int MB = COUT >= 128 ? 3 : (CIN == COUT || (CIN == 16 && COUT == 32)) ? 2 : 4;
+    static constexpr int MB_SMALL = 2;   // blocks per wave of the four-wave small-input form (NwOf)
+};
 
-// waves per SIMD the register budget is held to: 3 (<= 168 VGPRs) where it measured faster on
-// MI355X (the channel-doubling strided layer 32->64: a third resident workgroup per CU
-// shortens the last, partly filled round of tiles), 4 for 16->32, 2 elsewhere (3 costs spills there)
-template <int CIN, int COUT> struct MfmaOcc;
-
-// waves per workgroup: 8 for the 128-channel layers (one 32 KiB weight slab per offset then serves 384 sites
-// instead of 192: the slab stream through L2 is the largest term of those layers), 4 elsewhere
-#ifndef FNP_NW128
-#define FNP_NW128 8
-#endif
-#ifndef FNP_NW_MINCIN
-#define FNP_NW_MINCIN 128
-#endif
-#ifndef FNP_NW32
-#define FNP_NW32 8
-#endif
-#ifndef FNP_NW64
-#define FNP_NW64 8
-#endif
-template <int CIN, int COUT> struct MfmaWg { static constexpr int NW = (COUT == 128 && CIN >= FNP_NW_MINCIN) ? FNP_NW128 : (CIN == 32 && COUT == 32) ? FNP_NW32 : (CIN == 64 && COUT == 64) ? FNP_NW64 : 4; };
-
-#ifndef FNP_OCC1616
-#define FNP_OCC1616 4
-#endif
-#ifndef FNP_OCC3232
-#define FNP_OCC3232 4
-#endif
-#ifndef FNP_OCC6464
-#define FNP_OCC6464 4
-#endif
-#ifndef FNP_OCC128
-#define FNP_OCC128 2
-#endif
-template <int CIN, int COUT> struct MfmaOcc { static constexpr int WAVES = (CIN == 128 && COUT == 128) ? FNP_OCC128 : (CIN == 16 && COUT == 16) ? FNP_OCC1616 : (CIN == 32 && COUT == 32) ? FNP_OCC3232 : (CIN == 64 && COUT == 64) ? FNP_OCC6464 : (CIN == 16 && COUT == 32) ? 4 : ((CIN < COUT && COUT <= 64) || MfmaWg<CIN, COUT>::NW == 6) ? 3 : 2; };
+// waves per SIMD the register budget is held to: 4 for the 16/32/64-channel SubM layers and 16 -> 32; 3 (<= 168 VGPRs)
+// where it measured faster on MI355X (the channel-doubling strided layer 32 -> 64: a third resident workgroup per CU
+// shortens the last, partly filled round of tiles); 2 elsewhere (3 costs spills there)
+template <int CIN, int COUT> struct MfmaOcc { static constexpr int WAVES = (CIN == 128 && COUT == 128) ? 2 : (CIN == COUT || (CIN == 16 && COUT == 32)) ? 4 : (CIN < COUT && COUT <= 64) ? 3 : 2; };
 
 // FUSED (strided 3x3x3 layers of the fused backbone): the rulebook of such a layer is used exactly once, so the
 // kernel computes the 27 entries of its rows itself — each wave, at the top of a tile, one lane per row with the
@@ -329,8 +280,8 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
     static_assert(!FUSED || (KVOL == 27 && !WIN), "fused rulebook: 3x3x3 strided layers");
     constexpr int CH = Cfg::CH, SLAB = Cfg::SLAB, SW = Cfg::SW, KS = Cfg::KS, PFK = Cfg::PFK;
     constexpr bool ALLK = Cfg::ALLK;
-    constexpr int XLB = Cfg::XLB, WROWS = Cfg::win_rows(NWX, MB), WH = Cfg::WH;
-    static_assert(!WIN || ((CH == 4 || CH == 8) && XLB <= PFK && PFK % XLB == 0), "window path: 32/64 input channels");
+    constexpr int WROWS = Cfg::win_rows(NWX, MB), WH = Cfg::WH;
+    static_assert(!WIN || (CH == 8 && PFK == 1), "window path: 64 input channels, fragments read one offset ahead");
     constexpr int NB = COUT / 16;         // 16-channel output blocks
     constexpr int NBH = NB < 4 ? NB : 4;  // A fragments held at once
     constexpr int ROWS_PER_WAVE = MB * 16;
@@ -346,18 +297,11 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
     // 8-wave workgroups (128 -> 128): one chunk per thread and MFMA step, each held in a register for a whole
     // offset: chunk ks of W_{k+2} is requested at step ks of offset k and written to LDS at step ks of offset
     // k + 1, so the slab stream never waits for its own L2 latency (a step is ~0.15 us, the latency ~0.5-1 us)
-#ifndef FNP_WD4
-#define FNP_WD4 1
-#endif
-#ifndef FNP_WD4_64128
-#define FNP_WD4_64128 1
-#endif
     // (64 -> 128, four waves: 4 chunks per thread and slab, two per MFMA step — the same two-offsets-ahead register pipeline; its
     //  step-by-step staging left a one-scene launch waiting for the L2 once per offset: 33 us, 18.6 with no staging at all)
-    constexpr bool WD4 = FNP_WD4 && !ALLK && (((NW == 8 || (FNP_WD4_64128 && NW == 4 && CIN == 128 && COUT == 64)) && NCH == KS && NCH == 4) || (NWO == 4 && NCH == 2 * KS && KS == 4) ||
-                                              (FNP_WD4_64128 && NW == 4 && NCH == 2 * KS && KS == 2 && CIN == 64 && COUT == 128));
+    constexpr bool WD4 = !ALLK && (((NW == 8 || (NW == 4 && CIN == 128 && COUT == 64)) && NCH == KS && NCH == 4) || (NWO == 4 && NCH == 2 * KS && KS == 4) ||
+                                   (NW == 4 && NCH == 2 * KS && KS == 2 && CIN == 64 && COUT == 128));
     constexpr int WDN = WD4 ? NCH / KS : 1;   // chunks per thread and MFMA step (2 in the four-wave small-input form)
-    constexpr bool WPAIR = Cfg::WPAIR && WD4;
     static_assert(CIN % 16 == 0 && COUT % 16 == 0, "channel counts must be multiples of 16");
     static_assert(ALLK || SLAB % NT == 0 || SLAB < NT, "unsupported slab size");
 
@@ -368,27 +312,13 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
     // (16 consecutive rows x one logical chunk per quarter wave) are conflict-free
     unsigned char *const win = fnp_smem + Cfg::LDS_BYTES;
     constexpr unsigned WIN_ZERO = (unsigned)(Cfg::LDS_BYTES + WROWS * CH * 16);   // byte address of the zeros
-    auto win_sw = [](unsigned d) -> unsigned { return CH == 4 ? ((0u - (d >> 2)) & 3u) : ((d >> 1) & 7u); };
+    auto win_sw = [](unsigned d) -> unsigned { return (d >> 1) & 7u; };
 
     constexpr bool PAIR = Cfg::PAIR;
-#ifndef FNP_CONV_PRIO
-#define FNP_CONV_PRIO 0
-#endif
-#ifndef FNP_SWEEP_PRIO
-#define FNP_SWEEP_PRIO 0
-#endif
-#ifndef FNP_GPAIR
-#define FNP_GPAIR 1   // (round 5: 128 -> 128 class-sorted 0.765 -> 0.751 ms per launch at 128 scenes, 0.397 -> 0.390 at 64, conv_out -5 %; bit-identical)
-#endif
-    constexpr bool GPAIR = FNP_GPAIR && !WIN && KS % 2 == 0 && PFK == 1;
-#ifdef FNP_KLIM   // timing probe only (results are wrong): sweep the first FNP_KLIM offsets
-    const int K = KVOL > 0 ? (Cfg::KEFF < FNP_KLIM ? Cfg::KEFF : FNP_KLIM) : Krt;
-#else
+    // GPAIR: the two 64-byte halves of a 128-byte feature line are gathered back to back (128 -> 128 class-sorted
+    // 0.765 -> 0.751 ms per launch at 128 scenes, conv_out -5 %)
+    constexpr bool GPAIR = !WIN && KS % 2 == 0 && PFK == 1;
     const int K = KVOL > 0 ? Cfg::KEFF : Krt;   // (PAIR: offset pairs)
-#endif
-#if FNP_CONV_PRIO
-    __builtin_amdgcn_s_setprio(FNP_CONV_PRIO);   // (probe: convolution waves ahead of the index kernels that share the CUs in the replayed step)
-#endif
     const int n = min(*n_out, cap);
     const int tid = threadIdx.x;
     const int lane = tid & 63, wave = tid >> 6;
@@ -660,7 +590,7 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
         int rawq[PFK][MBT];   // raw rulebook entries of the offsets PFK..2*PFK-1 ahead (gathers of this round)
         int rawr[PFK][MBT];   // ... of the offsets 2*PFK..3*PFK-1 ahead (gathers of the next round)
         unsigned loff[WIN ? PFK : 1][WIN ? MBT : 1];          // window addresses of the fragments in xb
-        u32x4 xl[WIN ? XLB : 1][WIN ? KS : 1][WIN ? MBT : 1];  // window reads, XLB offsets ahead
+        u32x4 xl[WIN ? KS : 1][WIN ? MBT : 1];                // window reads, one offset ahead
 #pragma unroll
         for (int u = 0; u < PFK; ++u)
 #pragma unroll
@@ -673,37 +603,21 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
                 rawq[u][mb] = ent_raw(PFK + u, mb);
                 rawr[u][mb] = ent_raw(2 * PFK + u, mb);
             }
-        // L2 line touch (ranked rows): the input rows just above this tile — the next tile's own rows, first
-        // reached by the upper-neighbour offsets of this one — are requested one dword per 128-byte line now,
-        // so the gathers that reach them later in the sweep hit L2 instead of each paying a fabric round trip
-        // (VMEM returns in order: one late row holds back every younger gather of the wave, and the
-        // per-offset barrier passes that wait on to the whole workgroup).  The values are never used.
-        constexpr int NPF = (FNP_PF & 1) && !WIN && CIN == COUT ? (ROWS_PER_WG * CIN * 2 / 128 + NT - 1) / NT : 0;
-        unsigned pfv[NPF > 0 ? NPF : 1];
-        if constexpr (NPF > 0) {
-            const unsigned pbase = ((hints & FNP_HINT_ROWS_RANKED) ? (unsigned)(tile_base + NW * MBT * 16) * (unsigned)(CIN * 2) : 0x80000000u);
-#pragma unroll
-            for (int j = 0; j < NPF; ++j)
-                pfv[j] = __builtin_amdgcn_raw_buffer_load_b32(xrsrc, pbase + ((unsigned)tid + j * (unsigned)NT) * 128u, 0, 0);
-        }
         if (!ALLK) {
             if (!(FNP_ABLATE & 2)) {
 #pragma unroll
                 for (int j = 0; j < NCH; ++j) {
                     const int p = tid + j * NT;
                     if (SLAB % NT == 0 || p < SLAB) wl[st_pos0 + j * NT] = wslab(0)[p];
-                    if (WPAIR) wl[SLAB + st_pos0 + j * NT] = wslab(1)[p];
                 }
             }
             __syncthreads();
         }
         if constexpr (WIN) {
 #pragma unroll
-            for (int j = 0; j < XLB; ++j)
+            for (int ks = 0; ks < KS; ++ks)
 #pragma unroll
-                for (int ks = 0; ks < KS; ++ks)
-#pragma unroll
-                    for (int mb = 0; mb < MBT; ++mb) xl[j][ks][mb] = win_read(loff[j][mb] ^ (unsigned)(ks << 6));
+                for (int mb = 0; mb < MBT; ++mb) xl[ks][mb] = win_read(loff[0][mb] ^ (unsigned)(ks << 6));
         }
         // (named scalars, not an array: a conditionally written array lands in scratch memory)
         uint4 wcur0 = make_uint4(0u, 0u, 0u, 0u), wcur1 = make_uint4(0u, 0u, 0u, 0u);
@@ -716,7 +630,7 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
         uint4 wd0 = make_uint4(0u, 0u, 0u, 0u), wd1 = wd0, wd2 = wd0, wd3 = wd0;   // (named: see wcur0)
         uint4 we0 = wd0, we1 = wd0, we2 = wd0, we3 = wd0;                          // (WDN == 2: the second chunk of a step)
         if (WD4 && !(FNP_ABLATE & 2)) {
-            const uint4 *w1 = wslab(WPAIR ? 2 : 1);
+            const uint4 *w1 = wslab(1);
             wd0 = w1[tid]; wd1 = w1[tid + WDN * NT];
             if constexpr (KS > 2) { wd2 = w1[tid + 2 * WDN * NT]; wd3 = w1[tid + 3 * WDN * NT]; }
             if constexpr (WDN == 2) {
@@ -725,16 +639,13 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
             }
         }
         FNP_MS(2);
-#if FNP_SWEEP_PRIO
-        __builtin_amdgcn_s_setprio(FNP_SWEEP_PRIO);   // (probe: a sweeping workgroup's waves ahead of those of a workgroup in its prologue / epilogue)
-#endif
         for (int k0 = 0; k0 < Kt; k0 += PFK) {
 #pragma unroll
             for (int u = 0; u < PFK; ++u) {
                 const int k = k0 + u;
                 if (k >= Kt) break;  // wave-uniform
                 u32x4 xl_nx[WIN ? KS : 1][WIN ? MBT : 1];
-                const uint4 *wk = wl + (ALLK ? k : WPAIR ? (k & 3) : (k & 1)) * SLAB;
+                const uint4 *wk = wl + (ALLK ? k : (k & 1)) * SLAB;
                 const uint4 *wsrc = wslab(k + 1);
                 // rulebook entries for offset k + 3*PFK: requested FIRST in the round, so that they are
                 // older than this round's gathers (VMEM returns in order: a young index load in
@@ -762,11 +673,9 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
                 for (int ks = 0; ks < KS; ++ks) {
                     if (WD4 && !(FNP_ABLATE & 2)) {
                         uint4 &wd = ks == 0 ? wd0 : ks == 1 ? wd1 : ks == 2 ? wd2 : wd3;
-                        // chunk ks of W_{k+1} (WPAIR: of W_{k+2}, into the ring slot nobody has read since the last barrier)
-                        wl[(WPAIR ? ((k + 2) & 3) : ((k + 1) & 1)) * SLAB + st_pos0 + ks * WDN * NT] = wd;
-                        constexpr int AH = WPAIR ? 3 : 2;
-                        const uint4 *w2 = wslab(k + AH);
-                        wd = w2[tid + ks * WDN * NT];                                         // chunk ks of W_{k+2} (WPAIR: W_{k+3})
+                        wl[((k + 1) & 1) * SLAB + st_pos0 + ks * WDN * NT] = wd;               // chunk ks of W_{k+1}
+                        const uint4 *w2 = wslab(k + 2);
+                        wd = w2[tid + ks * WDN * NT];                                         // chunk ks of W_{k+2}
                         if constexpr (WDN == 2) {
                             uint4 &we = ks == 0 ? we0 : ks == 1 ? we1 : ks == 2 ? we2 : we3;
                             wl[((k + 1) & 1) * SLAB + st_pos0 + (ks * 2 + 1) * NT] = we;
@@ -799,21 +708,18 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
                             const uint4 t = wk[aoff[ks] + (h + j) * 16 * CH];
                             wa[j] = *reinterpret_cast<const bf16x8 *>(&t);
                         }
-                        // (3b) window fragments of offset k + XLB into the registers this step frees
+                        // (3b) window fragments of offset k + 1 into the registers this step frees
                         if constexpr (WIN) {
                             if (h + NBH >= NB) {
 #pragma unroll
-                                for (int mb = 0; mb < MBT; ++mb) {
-                                    const unsigned lo = XLB == PFK ? lnew[mb] : loff[(u + XLB) % PFK][mb];
-                                    xl_nx[ks][mb] = win_read(lo ^ (unsigned)(ks << 6));
-                                }
+                                for (int mb = 0; mb < MBT; ++mb) xl_nx[ks][mb] = win_read(lnew[mb] ^ (unsigned)(ks << 6));
                             }
                         }
 #pragma unroll
                         for (int mb = 0; mb < MBT; ++mb) {
                             bf16x8 xv = xb[u][ks][mb];
                             if constexpr (WIN) {
-                                const u32x4 t = *reinterpret_cast<const u32x4 *>(&xv) | xl[u % XLB][ks][mb];
+                                const u32x4 t = *reinterpret_cast<const u32x4 *>(&xv) | xl[ks][mb];
                                 xv = *reinterpret_cast<const bf16x8 *>(&t);
                             }
 #pragma unroll
@@ -828,13 +734,12 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
                     }
                     if constexpr (WIN) {
 #pragma unroll
-                        for (int mb = 0; mb < MBT; ++mb) xl[u % XLB][ks][mb] = xl_nx[ks][mb];
+                        for (int mb = 0; mb < MBT; ++mb) xl[ks][mb] = xl_nx[ks][mb];
                     }
                     // (4) the registers are free again: request the fragments of offset k + PFK (the
                     //     rulebook entry was loaded two rounds ago; validity is decided here)
                     if constexpr (GPAIR) {
-                        // (FNP_GPAIR: the two 64-byte halves of a 128-byte line requested back to back — behind the odd step — so that
-                        //  the second half finds the line in L1 instead of fetching it from L2 again)
+                        // (both halves of a line behind the odd step: the second finds the line in L1 instead of fetching it from L2 again)
                         if (ks & 1) {
 #pragma unroll
                             for (int mb = 0; mb < MBT; ++mb) {
@@ -875,19 +780,12 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
                         }
                     }
                     FNP_MS(0);
-                    if (!WPAIR || (k & 1) || k == Kt - 1) __syncthreads();  // plain loads stay in flight across it; only the LDS writes are waited for
+                    __syncthreads();  // plain loads stay in flight across it; only the LDS writes are waited for
                     FNP_MS(1);
                 }
             }
         }
 #undef FNP_LDS_POS
-#if FNP_SWEEP_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
-        if constexpr (NPF > 0) {
-#pragma unroll
-            for (int j = 0; j < NPF; ++j) asm volatile("" ::"v"(pfv[j]));
-        }
 
         // epilogue: lane holds out[site = row0 + mb*16 + l15][c0 .. c0+3], c0 = nb*16 + q*4
         // (window kernel: measured slower with either strip placement — 194 -> 200 / 214 us — and keeps the narrow form)
@@ -975,16 +873,12 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
                         if constexpr (SORTED) ro = orow[mb][h][i];
                         const u32x4 t = *reinterpret_cast<const u32x4 *>(eb + (i * SPI + wsite) * ES + wchunk * 16);
                         if (r < row_end && !(FNP_ABLATE & 128)) {
-#if FNP_NT_STORE
-                            __builtin_nontemporal_store(t, reinterpret_cast<u32x4 *>(y + (size_t)ro * COUT + wchunk * 8));
-#else
                             *reinterpret_cast<u32x4 *>(y + (size_t)ro * COUT + wchunk * 8) = t;
-#endif
                         }
                     }
                 }
             }
-        } else if constexpr (FNP_SWAP_EPI && (WIN || Cfg::WPAIR) && sizeof(TOut) == 2 && NB % 2 == 0) {
+        } else if constexpr (WIN && sizeof(TOut) == 2 && NB % 2 == 0) {
             // window kernel (its LDS is busy with the other resident workgroup's window reads: the strip form
             // measured slower): the 8-byte pieces of channel blocks k and k + 1 are exchanged between the lane
             // rows q, q ^ 1 of a site (v_permlane16_swap: odd rows of the first register <-> even rows of the
@@ -1142,24 +1036,8 @@ template <int CIN, int COUT, int KVOL, bool WIN, typename TOut, bool FUSED = fal
 int launch_mfma_k(const void *x, int x_bytes, const void *w, const int *nbr, int nbr_stride, int K, const int *n_out, int cap,
                   void *y, const float *scale, const float *shift, const void *residual, int relu, int hints, hipStream_t s,
                   const FusedRb *frb_in = nullptr, const SortedRb *srb_in = nullptr, int *grid_only = nullptr, const SplitOut *so_in = nullptr) {
-    // 16-site blocks per wave: 4 (64 sites); 3 for 128 output channels (accumulators = COUT/16 * MB * 4
-    // registers; 4 spills heavily, 3 spills ~16 registers outside the offset loop and measured 13 %
-    // faster than 2 on MI355X: fewer weight-slab sweeps per site); 2 for the 16 -> 16 layers
-#ifndef FNP_MB128
-#define FNP_MB128 3
-#endif
-    // (16 -> 32, 8 % of the pairs present: 2 blocks at 4 waves/SIMD measured 9 % faster than 4 blocks at 3)
-#ifndef FNP_MB3232
-#define FNP_MB3232 2
-#endif
-#ifndef FNP_MB_SMALL
-#define FNP_MB_SMALL 2   // (blocks per wave of the four-wave small-input form)
-#endif
-#ifndef FNP_MB6464
-#define FNP_MB6464 2
-#endif
     constexpr int NWX = NwOf<CIN, COUT, NWO>::value;
-    constexpr int MB = NWO ? FNP_MB_SMALL : COUT >= 128 ? FNP_MB128 : (CIN == 16 && COUT <= 32) ? 2 : (CIN == 32 && COUT == 32) ? FNP_MB3232 : (CIN == 64 && COUT == 64) ? FNP_MB6464 : 4;
+    constexpr int MB = NWO ? MfmaWg<CIN, COUT>::MB_SMALL : MfmaWg<CIN, COUT>::MB;
     using Cfg = MfmaCfg<CIN, COUT, KVOL>;
     auto kern = spconv_mfma_kernel<CIN, COUT, MB, KVOL, WIN, TOut, FUSED, TAct, SORTED, NWO>;
     constexpr int lds = Cfg::lds_bytes(NWX, MB, WIN) + Cfg::epi_bytes(NWX, WIN, sizeof(TOut) == 2) +
@@ -1195,11 +1073,7 @@ int launch_mfma_k(const void *x, int x_bytes, const void *w, const int *nbr, int
     // workgroups most CUs would idle while a few sweep MB blocks per wave — split finer instead, down to one 16-site
     // block per wave (the kernel runs such a range as a partial tile).  The split never changes results.
     const int fine = fnp_divup(cap, NWX * 16);
-#ifdef FNP_NO_FINE   // (development switch)
-    const int grid = tiles < resident ? tiles : resident;
-#else
     const int grid = tiles >= resident ? resident : (fine < resident ? fine : resident);
-#endif
     if (grid_only) {
         *grid_only = grid;
         return FNP_OK;
@@ -1216,17 +1090,7 @@ int launch_mfma_k(const void *x, int x_bytes, const void *w, const int *nbr, int
 // 64 -> 64 channels 132 -> 120 us; 32 -> 32 channels 78 -> 115 us (the per-fragment address
 // arithmetic and OR of the dual-source operand outweigh the saved gathers at 8 MFMAs per offset),
 // so only the 64-channel layers take it.
-#ifndef FNP_WIN32
-#define FNP_WIN32 0
-#endif
-#ifndef FNP_WIN64
-#define FNP_WIN64 1
-#endif
-#ifndef FNP_SMALL128
-#define FNP_SMALL128 1
-#endif
-#define FNP_MB128_DEFAULT 3
-template <int CIN, int COUT> struct HasWindow { static constexpr bool value = (FNP_WIN64 && CIN == 64 && COUT == 64) || (FNP_WIN32 && CIN == 32 && COUT == 32); };
+template <int CIN, int COUT> struct HasWindow { static constexpr bool value = CIN == 64 && COUT == 64; };
 
 template <int CIN, int COUT, typename TOut, typename TAct>
 int launch_mfma(const void *x, int x_bytes, const void *w, const int *nbr, int nbr_stride, int K, const int *n_out,
@@ -1240,7 +1104,7 @@ int launch_mfma(const void *x, int x_bytes, const void *w, const int *nbr, int n
         }
         if constexpr (CIN == 128 && COUT == 128 && sizeof(TOut) == 2) {
             // fewer rows than the persistent grid has 384-row tiles: the four-wave form (see NwOf)
-            if (cap < 256 * MfmaWg<CIN, COUT>::NW * FNP_MB128_DEFAULT * 16 && FNP_SMALL128)
+            if (cap < 256 * MfmaWg<CIN, COUT>::NW * MfmaWg<CIN, COUT>::MB * 16)
                 return launch_mfma_k<CIN, COUT, 27, false, TOut, false, TAct, false, 4>(x, x_bytes, w, nbr, nbr_stride, K, n_out, cap, y, scale, shift,
                                                                                         residual, relu, hints, s);
         }
@@ -1569,7 +1433,7 @@ extern "C" int fnp_rulebook_classsort(const int *nbr, int nbr_stride, int K, con
     const int rc = launch_mfma_k<128, 128, 27, false, __bf16, false, __bf16, true>(nullptr, 0, nullptr, nullptr, cap_out, 27, n_out, cap_out, nullptr, nullptr,
                                                                                     nullptr, nullptr, 0, 0, s, nullptr, nullptr, &grid);
     if (rc != FNP_OK) return rc;
-    constexpr int NW = MfmaWg<128, 128>::NW, TILE = NW * FNP_MB128 * 16;
+    constexpr int NW = MfmaWg<128, 128>::NW, TILE = NW * MfmaWg<128, 128>::MB * 16;
     const int slots = (grid >> 3) + ((grid & 7) ? 1 : 0);
     if ((long long)slots * TILE > (long long)kSortThreads * kSortQ) return FNP_ERR_ARG;   // (a round is placed by one workgroup)
     const int rounds = fnp_divup(fnp_divup(cap_out, 8) + 16 * (slots + 1), (long long)((grid >> 3) > 0 ? (grid >> 3) : 1) * TILE) + 1;
@@ -1589,22 +1453,18 @@ extern "C" int fnp_spconv_forward_sorted(const void *feat_in, int dtype, int n_i
     const long long xb = (long long)n_in_rows * Cin * 2;
     if (xb >= 0x7fffffffll) return FNP_ERR_ARG;
     const SortedRb srb{perm, blockmask};
-    // ROWS128 (round 7): launches that give every wave of the persistent grid at least one 16-row block take the LDS-DMA row
-    // pipeline of spconv_rows128.hip — the same tiles, rounds and sums (bit-identical); fewer rows (the one-scene path: a few
-    // thousand rows, part of the grid idle and the time in the slab stream, not the gathers) stay on the register pipeline below.
-    // -DFNP_ROWS128=0: the register pipeline for every launch (the A/B variant, tools/build_variant.sh).
-#ifndef FNP_ROWS128
-#define FNP_ROWS128 1
-#endif
-    if constexpr (FNP_ROWS128 && MfmaWg<128, 128>::NW == kSortedNW && FNP_MB128 == kSortedMB && MfmaOcc<128, 128>::WAVES == 2) {
-        if ((dtype == FNP_BF16 || dtype == FNP_F16) && cap_out >= 256 * kSortedNW * 16) {
-            int grid = 0;
-            const int rc = launch_mfma_k<128, 128, 27, false, __bf16, false, __bf16, true>(nullptr, 0, nullptr, nullptr, cap_out, 27, n_out, cap_out, nullptr,
-                                                                                            nullptr, nullptr, nullptr, 0, 0, (hipStream_t)stream, nullptr, nullptr, &grid);
-            if (rc != FNP_OK) return rc;
-            return fnp_launch_rows128(dtype, feat_in, weight, nbr, nbr_stride, n_out, cap_out, feat_out, scale, shift, residual, relu, perm, blockmask, grid,
-                                      (hipStream_t)stream);
-        }
+    // Launches that give every wave of the persistent grid at least one 16-row block take the LDS-DMA row pipeline of
+    // spconv_rows128.hip — the same tiles, rounds and sums (bit-identical); fewer rows (the one-scene path: a few thousand
+    // rows, part of the grid idle and the time in the slab stream, not the gathers) stay on the register pipeline below.
+    static_assert(MfmaWg<128, 128>::NW == kSortedNW && MfmaWg<128, 128>::MB == kSortedMB && MfmaOcc<128, 128>::WAVES == 2,
+                  "the row pipeline sweeps the sorted grid's tiles: its geometry is the one sortedsweep.h names");
+    if ((dtype == FNP_BF16 || dtype == FNP_F16) && cap_out >= 256 * kSortedNW * 16) {
+        int grid = 0;
+        const int rc = launch_mfma_k<128, 128, 27, false, __bf16, false, __bf16, true>(nullptr, 0, nullptr, nullptr, cap_out, 27, n_out, cap_out, nullptr,
+                                                                                        nullptr, nullptr, nullptr, 0, 0, (hipStream_t)stream, nullptr, nullptr, &grid);
+        if (rc != FNP_OK) return rc;
+        return fnp_launch_rows128(dtype, feat_in, weight, nbr, nbr_stride, n_out, cap_out, feat_out, scale, shift, residual, relu, perm, blockmask, grid,
+                                  (hipStream_t)stream);
     }
     if (dtype == FNP_BF16)
         return launch_mfma_k<128, 128, 27, false, __bf16, false, __bf16, true>(feat_in, (int)xb, weight, nbr, nbr_stride, 27, n_out, cap_out, feat_out, scale,

@@ -365,17 +365,11 @@ __global__ __launch_bounds__(kThreads) void pairs_emit_kernel(const int *__restr
 }
 
 // PAIRS: the rows of offset k come from the pair lists (pair_o / pair_i / pair_count) instead of a sweep over the table column
-#ifndef FNP_WGRAD_TR_NARROW
-#define FNP_WGRAD_TR_NARROW 128
-#endif
-#ifndef FNP_WGRAD_TR_WIDE
-#define FNP_WGRAD_TR_WIDE 64   // (128 x 128; 32 -> 64 rows per tile at the end of round 3: twice the MFMAs between two barriers, still two
-                                //  workgroups per CU: 142 -> 122 us per launch at 16 scenes — the kernel is bound by its per-tile round trip)
-#endif
 template <int CIN, int COUT> struct WgradTile {
     static constexpr int NBO = COUT / 16, WB = NBO >= 4 ? 4 : NBO, WK = 4 / WB;
-    // (two buffers x WK slices x rows x (dy row + x row + padding) must leave room for several workgroups per CU)
-    static constexpr int rows = (CIN + COUT >= 256) ? FNP_WGRAD_TR_WIDE : (CIN + COUT >= 192 || WK > 1) ? 64 : FNP_WGRAD_TR_NARROW;
+    // (two buffers x WK slices x rows x (dy row + x row + padding) must leave room for several workgroups per CU; 128 x 128 with
+    //  64 rows instead of 32: twice the MFMAs between two barriers, still two workgroups per CU, 142 -> 122 us per launch at 16 scenes)
+    static constexpr int rows = (CIN + COUT >= 192 || WK > 1) ? 64 : 128;
 };
 template <int CIN, int COUT, typename T16, bool PAIRS = false>
 __global__ __launch_bounds__(kThreads) void wgrad_mfma_kernel(const T16 *__restrict__ x, const T16 *__restrict__ dy,
@@ -582,18 +576,9 @@ void launch_wgrad_mfma(dim3 grid, hipStream_t s, const T16 *x, const T16 *dy, co
 // row chunks per offset (round 3: 128 / 64 / 32 -> 32 / 32 / 24 once the pair lists had halved the rows of an offset and the
 // tiles had grown: fewer partials to write and to add — the reduction pass reads chunks x K x Cin x Cout floats — and
 // 24 x 27 workgroups of the 128 x 128 layer are resident at once instead of a full round and a tail; -2 % of the step)
-#ifndef FNP_WG_CH1
-#define FNP_WG_CH1 32
-#endif
-#ifndef FNP_WG_CH2
-#define FNP_WG_CH2 32
-#endif
-#ifndef FNP_WG_CH3
-#define FNP_WG_CH3 24
-#endif
 static inline int max_chunks(int Cin, int Cout) {
     if ((long long)Cin * Cout <= 128) return 128;   // (wgrad_small_kernel, conv_input: one accumulator per thread — it needs the workgroups)
-    return (long long)Cin * Cout <= 4096 ? FNP_WG_CH1 : (long long)Cin * Cout <= 8192 ? FNP_WG_CH2 : FNP_WG_CH3;
+    return (long long)Cin * Cout <= 8192 ? 32 : 24;
 }
 
 template <typename TX, typename TY>

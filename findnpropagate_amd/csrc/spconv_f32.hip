@@ -242,13 +242,7 @@ int launch_f32(const void *x, long long x_bytes, const void *w, const int *nbr, 
     // sites per wave: 4 blocks up to 64 output channels (a weight fragment then serves 64 sites), 3 for 128
     // (accumulators = COUT/16 * MB * 4 registers; measured on MI355X at 64 scenes: 128 -> 128 4.54 -> 4.30 ms with 3
     // instead of 2, 64 -> 64 2.96 -> 2.68 ms with 4 instead of 2)
-#ifndef FNP_F32_MB128
-#define FNP_F32_MB128 3
-#endif
-#ifndef FNP_F32_MB64
-#define FNP_F32_MB64 4
-#endif
-    constexpr int MB = COUT <= 32 ? 4 : COUT == 64 ? FNP_F32_MB64 : FNP_F32_MB128;
+    constexpr int MB = COUT <= 64 ? 4 : 3;
     const int tiles = fnp_divup(cap, 4 * MB * 16);
     const int resident = 256 * F32Occ<COUT>::WAVES;      // one 4-wave workgroup per CU and wave slot
     const int fine = fnp_divup(cap, 4 * 16);            // small inputs: down to one 16-site block per wave

@@ -43,6 +43,13 @@
 #include "sortedsweep.h"
 #include <type_traits>
 
+// Instrument (development builds only; the shipped library has 0):
+//   FNP_R128_ABLATE  timing probes, a bit mask (results are wrong): 1 = no MFMA, 2 = no slab DMA, 4 = no row DMA, 8 = every row
+//                    piece fetches the line of zeros (same issue, one line per piece), 16 = no vmcnt wait inside the sweep
+#ifndef FNP_R128_ABLATE
+#define FNP_R128_ABLATE 0
+#endif
+
 namespace {
 
 __device__ uint4 g_rows128_zero[8];   // 128 bytes of zeros: the half row an absent neighbour fetches
@@ -57,10 +64,6 @@ template <int I, int N, typename F> __device__ __forceinline__ void fnp_static_f
 typedef __attribute__((address_space(1))) const void *fnp_gptr;
 typedef __attribute__((address_space(3))) void *fnp_lptr;
 
-#ifndef FNP_R128_ABLATE
-#define FNP_R128_ABLATE 0   // development timing probes (wrong results): 1 = no MFMA, 2 = no slab DMA, 4 = no row DMA, 8 = every row piece fetches the line of
-                            // zeros (same issue, one line per piece), 16 = no vmcnt wait inside the sweep
-#endif
 #define FNP_VMCNT(N) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory")
 #define FNP_LGKMCNT0() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 

@@ -25,8 +25,17 @@
 #include "tilerb.h"
 #include <type_traits>
 
-#ifndef FNP_NT_STORE
-#define FNP_NT_STORE 0   // (development: output rows stored with the non-temporal hint)
+// Instruments (development builds only; the shipped library has neither):
+//   FNP_TILE_ABLATE  timing probes, a bit mask (results are wrong): 1 = escape entries are taken as absent, 2 = consumers skip the
+//                    offset sweep, 4 = producers write the first two tiles only, 16 / 32 = consumers skip weight / fragment reads,
+//                    64 = no MFMA, 512 = no output stores; 64-channel kernel: 128 = the weight slabs are not streamed, 256 = no
+//                    barrier per offset, 1024 = every entry names the row of zeros (all 16 lanes of a read group share one address,
+//                    a broadcast: the sweep with its B-fragment reads free of bank conflicts), 2048 = the slabs are stored but not
+//                    loaded, 4096 = loaded but not stored
+//   FNP_TILE_STAMP   phase clocks: every wave sums the s_memtime ticks it spends in each phase of its role;
+//                    fnp_debug_tile_stamps() returns and clears the sums.  [role 0 = consumer, 1 = producer][phase]
+#ifndef FNP_TILE_ABLATE
+#define FNP_TILE_ABLATE 0
 #endif
 namespace {
 
@@ -51,6 +60,7 @@ constexpr int kRbBytes = kK * kTile * 2;                // the entries of a tile
 constexpr int kImgBytes = kXBytes + kRbBytes;           // one tile image
 constexpr int kLds = kWBytes + 2 * kImgBytes + 64 + 64; // + escape flags + hand-over counters
 constexpr int kRecFar = G32::REC_FAR, kRecEsc = G32::REC_ESC, kRecBytes = G32::REC;
+constexpr int kMB = G32::SPLIT, kNCW = 16 / kMB, kNPW = 8;   // 32-channel kernel: 16-row blocks per consumer wave, consumer and producer waves
 static_assert(kLds <= 160 * 1024, "LDS budget");
 static_assert(kTile == 256, "shape");
 __host__ __device__ constexpr unsigned row_code(unsigned rs) { return G32::code(rs); }
@@ -105,60 +115,6 @@ __global__ __launch_bounds__(256) void tile_rulebook_kernel(const int *__restric
     if (tid < 16) rec[G::REC_ESC + tid] = (unsigned char)esc[tid];
 }
 
-// Development-only timing probes (results are wrong; the shipped library has 0): 1 = escape entries are taken as absent,
-// 2 = consumers skip the offset sweep, 4 = producers write the first two tiles only, 16 / 32 = consumers skip weight / fragment reads,
-// 64 = no MFMA, 512 = no output stores; 64-channel kernel: 128 = the weight slabs are not streamed, 256 = no barrier per offset
-#ifndef FNP_TILE_ABLATE
-#define FNP_TILE_ABLATE 0
-#endif
-#ifndef FNP_TILE_SCHED
-#define FNP_TILE_SCHED 1
-#endif
-#ifndef FNP_TILE64_SCHED
-#define FNP_TILE64_SCHED 1
-#endif
-#ifndef FNP_TILE64_RESK
-#define FNP_TILE64_RESK 6   // residual rows are requested this many offsets before the sweep ends
-#endif
-#ifndef FNP_CONV_PRIO
-#define FNP_CONV_PRIO 0
-#endif
-#ifndef FNP_TILE32_PRIO
-#define FNP_TILE32_PRIO 0
-#endif
-// wave priority during the 64-channel kernel's offset sweep (round 5).  The two workgroups of a CU share its SIMDs wave by wave;
-// when one of them is between two sweeps — image and slab stores, residual loads, the epilogue's arithmetic and row stores — its
-// instructions compete at equal priority with the other one's matrix and LDS-read stream, which is what bounds the launch.  With
-// the sweep at priority 2 (the rest at 0): 0.607 -> 0.577 ms per launch at 128 scenes (-4.9 %; priority 1 / 3: 0.579 / 0.577;
-// tools/ab_tiled.py, interleaved, bit-identical).  The same switch on the 32-channel kernel's consumer waves (against its producer
-// waves) and on the gather kernels' sweeps measured within +-0.5 %: not taken there.
-#ifndef FNP_TILE64_PRIO
-#define FNP_TILE64_PRIO 2
-#endif
-#ifndef FNP_TILE64_WDEPTH
-#define FNP_TILE64_WDEPTH 2   // weight slabs in flight in registers (64-channel kernel)
-#endif
-#ifndef FNP_TILE64_STORE_AT
-#define FNP_TILE64_STORE_AT 6
-#endif
-#ifndef FNP_TILE64_SPREAD
-#define FNP_TILE64_SPREAD 2   // (1: one piece per offset from the sweep's second offset on — round 4; 2: two per offset behind the last slab requests — round 5)
-#endif
-#ifndef FNP_TILE32_NPW
-#define FNP_TILE32_NPW 8   // producer waves of the 32-channel kernel
-#endif
-#ifndef FNP_TILE_PSLEEP
-#define FNP_TILE_PSLEEP 8
-#endif
-#ifndef FNP_TILE_DW
-#define FNP_TILE_DW 1
-#endif
-#ifndef FNP_TILE_DX
-#define FNP_TILE_DX 2
-#endif
-
-// Development-only phase clocks (FNP_TILE_STAMP builds): every wave sums the s_memtime ticks it spends in each phase
-// of its role; fnp_debug_tile_stamps() returns and clears the sums.  [role 0 = consumer, 1 = producer][phase]
 #ifdef FNP_TILE_STAMP
 __device__ unsigned long long g_tile_stamps[4][8];   // [role][phase] sums, [2 + role][phase] maxima over waves
 #define FNP_STAMP_NOW(v)                                                       \
@@ -195,17 +151,12 @@ __device__ unsigned long long g_tile_stamps[4][8];   // [role][phase] sums, [2 +
 __device__ unsigned g_tile_aborts;   // hand-over waits that timed out, since the library was loaded (never, unless the protocol is broken)
 __device__ int g_tile_hold;          // test hook (fnp_debug_tile_hold): producers never publish an image, so every consumer wait times out
 
-// Geometry: NCW = 16 / MB consumer waves x (16 MB) rows, MB = FNP_TILE32_MB = 2 as shipped: consumer wave w owns tile rows
-// [32 w, 32 w + 32); its MFMA column l15 of block mb is row 32 w + MB l15 + mb, so the MB entries of a lane sit in one 32-bit (MB = 4:
-// 64-bit) word of the natural [offset][row] table.  Neighbours of such a column set are rows of ONE residue mod MB, so the window
-// image keeps the residues in separate parts (tilerb.h SPLIT): what a fragment read touches is then 16 consecutive 64-byte rows, as
-// in a dense tile.
-// MB = 4 (round 5; four consumer waves x 64 rows, 768 threads, 166 registers): a weight fragment read from LDS serves four row
-// blocks instead of two — 6.5 LDS reads per 8 MFMAs instead of 4.5 per 4, -28 % of the array cycles per flop, the remedy if the LDS
-// array (SQ_LDS_IDX_ACTIVE = 0.87 of the busy CU cycles, r04 PMC) were what bounds the kernel.  Bit-identical and SLOWER: 0.304
-// against 0.289 ms per launch at 128 scenes, 0.159 against 0.152 at 64 (tools/ab_tiled.py, interleaved in one process; four
-// producer waves instead of eight: 0.304 / 0.164) — ONE consumer wave per SIMD has nobody to issue into its waits, which costs more
-// than the array cycles saved.  Kept as a build switch with the numbers.
+// Geometry: kNCW = 8 consumer waves x 32 rows: consumer wave w owns tile rows [32 w, 32 w + 32); its MFMA column l15 of block mb is
+// row 32 w + 2 l15 + mb, so the two entries of a lane sit in one 32-bit word of the natural [offset][row] table.  Neighbours of such
+// a column set are rows of ONE parity, so the window image keeps even and odd rows in separate parts (tilerb.h SPLIT): what a
+// fragment read touches is then 16 consecutive 64-byte rows, as in a dense tile.  (Four consumer waves x 64 rows: fewer LDS reads
+// per MFMA, bit-identical and 5 % slower, 0.304 against 0.289 ms per launch at 128 scenes — ONE consumer wave per SIMD has nobody
+// to issue into its waits.)
 // X3 (fnp_spconv_forward_tiled_split, the bf16x3 engine's main product): the epilogue keeps f32 — f32 residual in, a 16-bit addend
 // (the two cross terms) joined before the ReLU, f32 rows out AND their (hi, lo) 16-bit split, the next layer's operands.  The
 // kernel's own y / residual are unused then.
@@ -243,7 +194,7 @@ __device__ __forceinline__ void x3_store(const X3Args &a, size_t elem, float (&v
 }
 
 template <typename TAct, bool X3 = false>
-__global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / FNP_TILE32_MB + FNP_TILE32_NPW) / 4) void spconv_tile32_kernel(const TAct *__restrict__ x, int x_bytes, const TAct *__restrict__ w,
+__global__ __launch_bounds__((kNCW + kNPW) * 64, (kNCW + kNPW) / 4) void spconv_tile32_kernel(const TAct *__restrict__ x, int x_bytes, const TAct *__restrict__ w,
                                                                  const unsigned char *__restrict__ tile_rb, int rb_bytes,
                                                                  const int *__restrict__ nbr, int nbr_stride,
                                                                  const int *__restrict__ n_out, int cap, TAct *__restrict__ y,
@@ -251,8 +202,7 @@ __global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / F
                                                                  const TAct *__restrict__ residual, int relu, X3Args x3) {
     using frag8 = typename V16<TAct>::v8;
     using act4 = typename V16<TAct>::v4;
-    constexpr int MB = FNP_TILE32_MB, NCW = 16 / MB, NPW = FNP_TILE32_NPW, NT = (NCW + NPW) * 64, PT = NPW * 64, NB = kC / 16;
-    static_assert(MB == 2 || MB == 4, "consumer tile");
+    constexpr int MB = kMB, NCW = kNCW, NPW = kNPW, NT = (NCW + NPW) * 64, PT = NPW * 64, NB = kC / 16;
     constexpr int NWL = (kWin * kCH + PT - 1) / PT;          // window chunks per producer thread
     constexpr int NCL = (kRbBytes / 16 + PT - 1) / PT;       // entry-table chunks per producer thread
     constexpr int NGL = kOvf / NPW / 16;                     // overflow-row loads per producer thread (4 lanes per row)
@@ -282,7 +232,7 @@ __global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / F
                 return false;
             }
             // (a poll is an LDS read in the consumers' queue: the producers, a tile ahead, poll slowly)
-            if (which >= FREED) __builtin_amdgcn_s_sleep(FNP_TILE_PSLEEP);
+            if (which >= FREED) __builtin_amdgcn_s_sleep(8);
             else __builtin_amdgcn_s_sleep(1);
         }
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
@@ -293,9 +243,6 @@ __global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / F
         if ((threadIdx.x & 63) == 0) __hip_atomic_fetch_add(&cnt[which], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
 
-#if FNP_CONV_PRIO
-    __builtin_amdgcn_s_setprio(FNP_CONV_PRIO);   // (probe: convolution waves ahead of the index kernels that share the CUs in the replayed step)
-#endif
     const int n = min(*n_out, cap);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, q = lane >> 4;
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void *)x, 0, x_bytes, 0x00020000);
@@ -410,10 +357,6 @@ __global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / F
             }
     }
     __syncthreads();   // weights, zero rows, counters
-#if FNP_TILE32_PRIO
-    __builtin_amdgcn_s_setprio(FNP_TILE32_PRIO);   // (the consumer waves — matrix work and LDS reads — ahead of the producers' data movement)
-#endif
-    if ((FNP_TILE_SCHED == 2 || FNP_TILE_SCHED == 3) && wave >= 4) __builtin_amdgcn_s_sleep(4);
     FNP_STAMP_DECL;
     for (int t = t_begin; t < t_end; ++t) {
         const int tile_base = t * kTile, row_end = min(n, tile_base + kTile);
@@ -421,9 +364,8 @@ __global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / F
         if (!wait_for(READY + image, NPW * ((t - t_begin) / 2 + 1))) break;
         FNP_STAMP(2);
         const unsigned char *img = img0 + image * kImgBytes;
-        // the MB entries of a lane's rows are MB consecutive 16-bit words of the [offset][row] table
-        using ent_t = typename std::conditional<MB == 4, unsigned long long, unsigned>::type;
-        const ent_t *rbE = reinterpret_cast<const ent_t *>(img + kXBytes) + wave * 16 + l15;
+        // the two entries of a lane's rows are consecutive 16-bit words of the [offset][row] table
+        const unsigned *rbE = reinterpret_cast<const unsigned *>(img + kXBytes) + wave * 16 + l15;
         // residual rows requested now, used after the sweep
         uint4 rv[MB];
 #pragma unroll
@@ -437,7 +379,7 @@ __global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / F
         for (int nb = 0; nb < NB; ++nb)
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) acc[nb][mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
-        auto entry = [&](int k) -> ent_t { return rbE[(k < kK ? k : kK - 1) * (kTile / MB)]; };
+        auto entry = [&](int k) -> unsigned { return rbE[(k < kK ? k : kK - 1) * (kTile / MB)]; };
         auto weights = [&](int k, frag8 (&wa)[NB]) {
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
@@ -448,10 +390,10 @@ __global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / F
         // The sweep: weights one offset ahead, fragments two, entries four.  ESC: this wave's entries may hold escapes.
         auto sweep = [&](auto esc_tag) {
             constexpr bool ESC = decltype(esc_tag)::value;
-            auto fragments = [&](ent_t e, int k, u32x4 (&xv)[MB]) {
+            auto fragments = [&](unsigned e, int k, u32x4 (&xv)[MB]) {
 #pragma unroll
                 for (int mb = 0; mb < MB; ++mb) {
-                    const unsigned em = (unsigned)(e >> (16 * mb)) & 0xffffu;
+                    const unsigned em = (e >> (16 * mb)) & 0xffffu;
                     if constexpr (ESC) {
                         if (__ballot(em == kEscape) != 0ull) {
                             // more far rows than overflow slots: this fragment comes from memory
@@ -469,8 +411,8 @@ __global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / F
                 }
             };
             // LDS reads run ahead of the matrix work: weights DW offsets, fragments DX, entries DX + 2
-            constexpr int DW = FNP_TILE_DW, DX = FNP_TILE_DX;
-            ent_t en[2];
+            constexpr int DW = 1, DX = 2;
+            unsigned en[2];
             frag8 wa[DW + 1][NB];
             u32x4 xf[DX + 1][MB];
 #pragma unroll
@@ -482,9 +424,8 @@ __global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / F
 #pragma unroll
             for (int k = 0; k < ((FNP_TILE_ABLATE & 2) ? 0 : kK); ++k) {
                 if (!(FNP_TILE_ABLATE & 16)) weights(k + DW, wa[(k + DW) % (DW + 1)]);
-                const ent_t e_new = (FNP_TILE_ABLATE & 32) ? en[0] : entry(k + DX + 2);
+                const unsigned e_new = (FNP_TILE_ABLATE & 32) ? en[0] : entry(k + DX + 2);
                 if (k + DX < kK && !(FNP_TILE_ABLATE & 32)) fragments(en[(k + DX) & 1], k + DX, xf[(k + DX) % (DX + 1)]);
-                if constexpr (!ESC && FNP_TILE_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                 for (int mb = 0; mb < MB; ++mb) {
                     const frag8 xv = *reinterpret_cast<const frag8 *>(&xf[(FNP_TILE_ABLATE & 32) ? 0 : k % (DX + 1)][mb]);
@@ -494,21 +435,7 @@ __global__ __launch_bounds__((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64, (16 / F
                         else acc[nb][mb] = tmfma(wa[(FNP_TILE_ABLATE & 16) ? 0 : k % (DW + 1)][nb], xv, acc[nb][mb]);
                     }
                 }
-                if constexpr (!ESC && FNP_TILE_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
-                if constexpr (!ESC && FNP_TILE_SCHED != 0 && MB == 4) {
-                    // one iteration = 8 MFMAs with the 7 LDS reads (2 weight fragments, 4 row fragments, the entry word) and their
-                    // address arithmetic spread between them, one read per MFMA: the ONE consumer wave of a SIMD has nobody to
-                    // fill its gaps, and reads bunched together queue up in the LDS array (measured on the 64-channel kernel, round 5)
-#pragma unroll
-                    for (int i = 0; i < 7; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
-                        __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);   // VALU
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                    __builtin_amdgcn_sched_barrier(0);   // (nothing moves between iterations: the read-ahead distances stand)
-                }
-                if constexpr (!ESC && FNP_TILE_SCHED != 0 && MB == 2) {
+                if constexpr (!ESC) {
                     // one iteration = 4 MFMAs with the 5 LDS reads and their address arithmetic spread between them: the two
                     // consumer waves of a SIMD then keep both pipes busy instead of bursting into each in turn
                     __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
@@ -623,9 +550,6 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
     unsigned char *const img = smem + 2 * SLABC * 16;
     int *const esc_flags = reinterpret_cast<int *>(img + XB + EB);
 
-#if FNP_CONV_PRIO
-    __builtin_amdgcn_s_setprio(FNP_CONV_PRIO);   // (probe: convolution waves ahead of the index kernels that share the CUs in the replayed step)
-#endif
     const int n = min(*n_out, cap);
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, l15 = lane & 15, q = lane >> 4;
     const __amdgpu_buffer_rsrc_t xrsrc = __builtin_amdgcn_make_buffer_rsrc((void *)x, 0, x_bytes, 0x00020000);
@@ -669,10 +593,10 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
     int *const id_lds = reinterpret_cast<int *>(img + XB + EB + 16);   // [OVF] far-row ids of the tile being requested
     float *const ss_lds = reinterpret_cast<float *>(img + XB + EB + 16 + G::OVF * 4);   // [2][C] BatchNorm scale, shift (read per tile from LDS, not L2)
     if (tid < 2 * C) ss_lds[tid] = scale ? (tid < C ? scale[tid] : shift[tid - C]) : (tid < C ? 1.f : 0.f);
-    // The next tile's image is requested in PIECES (FNP_TILE64_SPREAD, round 4): vector-memory loads return in order, so behind one
+    // The next tile's image is requested in PIECES: vector-memory loads return in order, so behind one
     // burst of all 14 image loads the weight slab requested at the sweep's first offset — waited for at its second — came back
-    // only after the whole image (~42 KB per workgroup) had arrived; one piece per offset, issued behind that offset's slab
-    // request, keeps every such wait one load deep.
+    // only after the whole image (~42 KB per workgroup) had arrived; the pieces go out behind the sweep's last slab requests
+    // (LATE PIECES below).
     constexpr int NPIECE = NWL + NEL + NOL;
     auto req_piece = [&](int t, int j) {
         const unsigned ro = rec_off(t);
@@ -721,7 +645,7 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
         // offset k, so a wave leaves the barrier with everything its next 16 MFMAs need in registers; slab k + 2 is stored
         // (slot k & 1, whose fragments were read an offset ago) during offset k, requested from L2 an offset before that.
         // Slabs 0 - 2 are requested before the image is written: they land meanwhile.
-        constexpr int WD = FNP_TILE64_WDEPTH;   // slabs on their way to LDS in registers (slab j in wslab[j % WD])
+        constexpr int WD = 2;   // slabs on their way to LDS in registers (slab j in wslab[j % WD]); a third adds nothing (0.592 against 0.593 ms)
         u32x4 wreg[2][NSL], wslab[WD][NSL];
         if (FNP_TILE_ABLATE & 2048) {
 #pragma unroll
@@ -746,10 +670,9 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
         // (the far-row ids of the NEXT tile pass through LDS here, under the same barrier as the image: their readers — the overflow
         //  pieces requested late in this sweep — come behind it, their previous readers finished before the barrier above; round 5:
         //  one workgroup barrier per tile less)
-        if (FNP_TILE64_SPREAD && tid < G::OVF) id_lds[tid] = t + 1 < t_end ? far_id : -1;
+        if (tid < G::OVF) id_lds[tid] = t + 1 < t_end ? far_id : -1;
         __syncthreads();
         FNP_STAMP(2);   // (image + slabs 0, 1 -> LDS, barrier)
-        if (!FNP_TILE64_SPREAD) req_tile(t + 1);   // (one more barrier inside: the ids' pass through LDS)
         req_far_ids(t + 2);
         FNP_STAMP(3);   // (next tile requested)
         f32x4 acc[NB][MB];
@@ -758,8 +681,6 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
 #pragma unroll
             for (int mb = 0; mb < MB; ++mb) acc[nb][mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
         const unsigned *rb32 = reinterpret_cast<const unsigned *>(img + XB) + wave * 16 + l15;   // both blocks' entries
-        // (FNP_TILE_ABLATE & 1024, timing probe, wrong results: every entry names the row of zeros — all 16 lanes of a read group then
-        //  share one address, a broadcast — i.e. the sweep with its B-fragment reads free of bank conflicts)
         auto entry = [&](int k) -> unsigned {
             const unsigned e = rb32[(k < kK ? k : kK - 1) * (G::TILE / 2)];
             return (FNP_TILE_ABLATE & 1024) ? ((e & 0u) | (G::code(G::ZERO) * 0x10001u)) : e;
@@ -779,7 +700,6 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
         if (FNP_TILE_ABLATE & 2) req_residual();
         auto sweep = [&](auto esc_tag) {
             constexpr bool ESC = decltype(esc_tag)::value;
-            constexpr bool kStoreEarly = !ESC && FNP_TILE64_SCHED == 2;
             // fragments of one offset: [ks][mb]; lane (l15, q) takes chunk 4 ks + q of its row
             auto fragments = [&](unsigned e, int k, u32x4 (&xv)[KS][MB]) {
 #pragma unroll
@@ -830,31 +750,21 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
                     for (int j = 0; j < NSL; ++j)
                         wslab[(k + 1) % WD][j] = __builtin_amdgcn_raw_buffer_load_b128(wrsrc, (unsigned)(tid + j * NT) * 16u, (unsigned)(k + WD + 1) * (C * C * 2), 0);
                 }
-                if (FNP_TILE64_SPREAD == 1 && k >= 1 && k <= NPIECE) req_piece(t + 1, k - 1);
-                if (FNP_TILE64_SPREAD == 2) {
-                    // LATE PIECES (round 5).  The image pieces are the only loads of the sweep that go to HBM (~2 us); issued one per
-                    // offset from the second offset on they sat, in the wave's in-order memory queue, IN FRONT of every weight-slab
-                    // load of offsets 2-15 — L2 hits that then returned with the HBM latency of the piece ahead of them (probes at
-                    // 128 scenes: no slab loads -12 % of the launch, no slab stores -5 %).  Now two per offset in the LAST seven
-                    // offsets, behind the sweep's last slab requests; the epilogue and the other workgroup of the CU cover their
-                    // latency, and the 56 prefetch registers are free for most of the sweep (256 registers with 2 spilt -> 243, none):
-                    // 0.610 -> 0.593 ms per launch at 128 scenes, 0.313 -> 0.301 at 64, 50.2 -> 48.3 us at 8 (tools/ab_tiled.py,
-                    // interleaved; bit-identical).  A third slab in flight on top (FNP_TILE64_WDEPTH 3) adds nothing (0.592 / 0.305).
-                    constexpr int K0 = kK - (NPIECE + 1) / 2;
-                    if (k >= K0) {
-                        req_piece(t + 1, 2 * (k - K0));
-                        if (2 * (k - K0) + 1 < NPIECE) req_piece(t + 1, 2 * (k - K0) + 1);
-                    }
+                // LATE PIECES.  The image pieces are the only loads of the sweep that go to HBM (~2 us): two per offset in the LAST
+                // seven offsets, behind the sweep's last slab requests, so that no weight-slab load (an L2 hit) waits in the wave's
+                // in-order memory queue behind the HBM latency of a piece; the epilogue and the other workgroup of the CU cover
+                // their latency, and the 56 prefetch registers are free for most of the sweep.  Against one piece per offset from
+                // the second offset on: 0.610 -> 0.593 ms per launch at 128 scenes, 0.313 -> 0.301 at 64, 50.2 -> 48.3 us at 8.
+                constexpr int K0 = kK - (NPIECE + 1) / 2;
+                if (k >= K0) {
+                    req_piece(t + 1, 2 * (k - K0));
+                    if (2 * (k - K0) + 1 < NPIECE) req_piece(t + 1, 2 * (k - K0) + 1);
                 }
-                if (k == kK - FNP_TILE64_RESK) req_residual();
+                if (k == kK - 6) req_residual();   // six offsets before the sweep ends
                 const unsigned e_new = entry(k + 3);
                 if (k + 1 < kK) {
                     fragments(en[(k + 1) & 1], k + 1, xf[(k + 1) & 1]);
                     weights(k + 1, wa[(k + 1) & 1]);
-                }
-                if (kStoreEarly && k + 2 < kK && !(FNP_TILE_ABLATE & (128 | 4096))) {
-#pragma unroll
-                    for (int j = 0; j < NSL; ++j) *reinterpret_cast<u32x4 *>(&wl[(k & 1) * SLABC + st_pos + j * NT]) = wslab[(k + 2) % WD][j];
                 }
                 // the 12 LDS reads of offset k + 1 interleaved with the 16 MFMAs of offset k and nothing moved across: left to
                 // itself the scheduler sinks every read to just before its first use and the wave waits for LDS four times an offset
@@ -866,17 +776,12 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
 #pragma unroll
                         for (int nb = 0; nb < NB; ++nb) acc[nb][mb] = tmfma(wa[k & 1][ks][nb], xv, acc[nb][mb]);
                     }
-                if constexpr (!ESC && FNP_TILE64_SCHED) {
+                if constexpr (!ESC) {
 #pragma unroll
                     for (int i = 0; i < 12; ++i) {
                         __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);   // MFMA
                         __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);   // DS read
                         __builtin_amdgcn_sched_group_barrier(0x002, 1, 0);   // VALU (fragment addresses)
-                        // (SCHED 2, measured and NOT taken: the slab stores in the middle of the block instead of behind its last MFMA, so that
-                        //  the barrier's LDS drain finds them done — legal at any point of offset k, slot k & 1 was last read during offset
-                        //  k - 1.  0.555 -> 0.587 ms per launch at 128 scenes behind MFMA 6; with a third slab in flight 0.566 / 0.559 /
-                        //  0.579 behind MFMA 6 / 9 / 2: the stores are cheapest where nothing else wants the LDS, at the end.  Round 5)
-                        if (FNP_TILE64_SCHED == 2 && i == FNP_TILE64_STORE_AT) __builtin_amdgcn_sched_group_barrier(0x200, 2, 0);
                     }
                     __builtin_amdgcn_sched_group_barrier(0x008, 4, 0);
                     __builtin_amdgcn_sched_barrier(0);
@@ -884,7 +789,8 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
                 en[(k + 1) & 1] = e_new;
                 if ((FNP_TILE_ABLATE & 4096) && k + 2 < kK) asm volatile("" ::"v"(wslab[(k + 2) % WD][0]), "v"(wslab[(k + 2) % WD][NSL - 1]));
                 if (k + 1 < kK) {
-                    if (!kStoreEarly && k + 2 < kK && !(FNP_TILE_ABLATE & (128 | 4096))) {   // (4096: probe — the slabs are loaded but not stored)
+                    // (the slab stores behind the block's last MFMA, where nothing else wants the LDS: in its middle 0.555 -> 0.587 ms per launch)
+                    if (k + 2 < kK && !(FNP_TILE_ABLATE & (128 | 4096))) {
 #pragma unroll
                         for (int j = 0; j < NSL; ++j) *reinterpret_cast<u32x4 *>(&wl[(k & 1) * SLABC + st_pos + j * NT]) = wslab[(k + 2) % WD][j];
                     }
@@ -892,14 +798,14 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
                 }
             }
         };
-#if FNP_TILE64_PRIO
-        __builtin_amdgcn_s_setprio(FNP_TILE64_PRIO);   // (the sweeping workgroup's waves ahead of the other workgroup's staging / epilogue waves)
-#endif
+        // The two workgroups of a CU share its SIMDs wave by wave; when one of them is between two sweeps — image and slab stores,
+        // residual loads, the epilogue — its instructions compete with the other one's matrix and LDS-read stream, which is what
+        // bounds the launch.  The sweep at priority 2, the rest at 0: 0.607 -> 0.577 ms per launch at 128 scenes (1 / 3: 0.579 /
+        // 0.577); on the 32-channel kernel's consumer waves and on the gather kernels' sweeps within +-0.5 %: not taken there.
+        __builtin_amdgcn_s_setprio(2);
         if (esc_flags[wave]) sweep(std::true_type{});
         else sweep(std::false_type{});
-#if FNP_TILE64_PRIO
-        __builtin_amdgcn_s_setprio(FNP_CONV_PRIO);
-#endif
+        __builtin_amdgcn_s_setprio(0);
         FNP_STAMP(4);   // (sweep)
 
         // epilogue: the arithmetic of spconv_mfma_kernel (scale / shift, residual, ReLU, one rounding), 16 bytes per lane
@@ -961,14 +867,8 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
                 }
                 auto t0 = __builtin_amdgcn_permlane16_swap(o[0].x, o[1].x, false, false);
                 auto t1 = __builtin_amdgcn_permlane16_swap(o[0].y, o[1].y, false, false);
-                if (live) {
-#if FNP_NT_STORE
-                    typedef unsigned int nt4 __attribute__((ext_vector_type(4)));
-                    __builtin_nontemporal_store((nt4){t0[0], t1[0], t0[1], t1[1]}, reinterpret_cast<nt4 *>(reinterpret_cast<unsigned char *>(y) + (size_t)r * (C * 2) + kp * 64 + poff));
-#else
+                if (live)
                     *reinterpret_cast<uint4 *>(reinterpret_cast<unsigned char *>(y) + (size_t)r * (C * 2) + kp * 64 + poff) = make_uint4(t0[0], t1[0], t0[1], t1[1]);
-#endif
-                }
             }
         }
         FNP_STAMP(5);   // (epilogue)
@@ -1009,7 +909,7 @@ int launch_tile32(const void *x, long long x_bytes, const void *w, const void *t
     }
     const int tiles = fnp_divup(cap, kTile);
     const int grid = tiles < 256 ? tiles : 256;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3((16 / FNP_TILE32_MB + FNP_TILE32_NPW) * 64), kLds, s, (const TAct *)x, (int)x_bytes, (const TAct *)w, (const unsigned char *)tile_rb, (int)rb_bytes,
+    hipLaunchKernelGGL(kern, dim3(grid), dim3((kNCW + kNPW) * 64), kLds, s, (const TAct *)x, (int)x_bytes, (const TAct *)w, (const unsigned char *)tile_rb, (int)rb_bytes,
                        nbr, nbr_stride, n_out, cap, (TAct *)y, scale, shift, (const TAct *)residual, relu, x3);
     FNP_LAUNCH_CHECK();
     return FNP_OK;

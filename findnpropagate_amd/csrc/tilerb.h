@@ -4,10 +4,6 @@
 #pragma once
 #include "common.h"
 
-#ifndef FNP_TILE32_MB
-#define FNP_TILE32_MB 2   // (4: four consumer waves x 64 rows — built, bit-identical, 5 % slower: round 5, spconv_tile.hip)
-#endif
-
 namespace tilerb {
 
 constexpr int kK = 27;                  // 3x3x3 kernels only
@@ -19,10 +15,10 @@ constexpr unsigned kEscape = 0xFFFFu;   // entry: not in the tile image — fetc
 // 16 consecutive image rows), OVF overflow rows (far neighbours, one slot per distinct row), one row of zeros.
 struct G32 {   // 32 channels: 64-byte rows.  (window +-64 with 128 overflow rows fits LDS too and was slower: 0.20 vs 0.18 ms per
                // layer, rulebook pass 0.27 vs 0.20 ms — 39 distinct far rows crowd a 128-slot table)
-    // SPLIT = 16-row blocks a consumer wave of spconv_tile32_kernel owns (FNP_TILE32_MB): its MFMA column l15 of block mb is tile row
+    // SPLIT = 16-row blocks a consumer wave of spconv_tile32_kernel owns: its MFMA column l15 of block mb is tile row
     // SPLIT l15 + mb of the wave's rows, so the neighbours of one block are rows of ONE residue mod SPLIT: the window keeps the
     // residues in separate parts, and what a fragment read touches is 16 consecutive image rows.
-    static constexpr int TILE = FNP_TILE_ROWS, HALO = 32, WIN = TILE + 2 * HALO, OVF = 256, ZERO = WIN + OVF, ROWB = 64, SPLIT = FNP_TILE32_MB;
+    static constexpr int TILE = FNP_TILE_ROWS, HALO = 32, WIN = TILE + 2 * HALO, OVF = 256, ZERO = WIN + OVF, ROWB = 64, SPLIT = 2;
     static constexpr int REC_FAR = kK * TILE * 2, REC_ESC = REC_FAR + OVF * 4, REC = REC_ESC + 16;
     // the row at slot rs stores logical chunk c (0..3) at chunk c ^ (-(rs >> 2) & 3)
     __host__ __device__ static constexpr unsigned code(unsigned rs) { return rs * ROWB + (((0u - (rs >> 2)) & 3u) << 4); }

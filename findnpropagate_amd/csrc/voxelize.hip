@@ -79,7 +79,7 @@ __global__ __launch_bounds__(kThreads) void vox_mark_kernel(const float *__restr
         if (z == 0 && (long long)gridDim.x * kThreads <= n) cnt[n] = 0;   // (n a multiple of the workgroup size)
     }
     __shared__ MarkTab tab;   // the marks of the workgroup's 256 points meet here first (rankgrid.h): one atomic per distinct block
-    if (FNP_MARK_TAB) mark_tab_init(&tab, threadIdx.x, kThreads);
+    mark_tab_init(&tab, threadIdx.x, kThreads);
     const int i = blockIdx.x * kThreads + threadIdx.x;   // (whole waves stay: the shuffles below need them.  Plain workgroup order: XCD-contiguous
                                                          //  runs — common.h — made this kernel's atomics 26 % slower, round 5)
     const int lane = fnp_lane();
@@ -121,8 +121,8 @@ __global__ __launch_bounds__(kThreads) void vox_mark_kernel(const float *__restr
         if (lane >= d && nb == blk) m |= nm;
     }
     const long long nxt = __shfl_down(blk, 1);
-    if (blk >= 0 && (lane == 63 || nxt != blk)) mark_put(FNP_MARK_TAB ? &tab : nullptr, g, blk, m);
-    if (FNP_MARK_TAB) mark_tab_flush(&tab, g, threadIdx.x, kThreads);
+    if (blk >= 0 && (lane == 63 || nxt != blk)) mark_put(&tab, g, blk, m);
+    mark_tab_flush(&tab, g, threadIdx.x, kThreads);
 }
 
 __global__ __launch_bounds__(kThreads) void vox_insert_kernel(int n, int maxp, int cap,
@@ -377,59 +377,7 @@ __device__ __forceinline__ void vox_write_row(const float *__restrict__ pts, int
     }
 }
 
-// CELL form (rounds 1-5; FNP_VOX_EMIT=cell): a thread per occupied cell in RANK order.  Everything behind the cell's slot list is a
-// scattered access: code and first-come rank of its first point, its points' rows, and the voxel row it writes (first-come order).
-__global__ __launch_bounds__(kThreads) void vox_emit_kernel(const float *__restrict__ pts, int C, int maxp,
-                                                            const int *__restrict__ boff, int B, int max_voxels,
-                                                            RankGridDims g, const long long *__restrict__ code,
-                                                            const int *__restrict__ top, const int *__restrict__ cnt,
-                                                            const int *__restrict__ fc, const int *__restrict__ scene,
-                                                            const int *__restrict__ n_sorted, int cap,
-                                                            int *__restrict__ perm, int *__restrict__ coords,
-                                                            int *__restrict__ num_points, float *__restrict__ mean,
-                                                            float *__restrict__ voxels, int *__restrict__ n_cells,
-                                                            int *__restrict__ n_dropped) {
-    const int ns = min(*n_sorted, cap);
-    const int *fc_start = scene;
-    const int *out_base = scene + (B + 1);
-    if (n_cells && blockIdx.x == 0 && threadIdx.x == 0) *n_cells = ns;
-    // ranks beyond the occupied cells map to no row (consumers walk perm[0 .. cap))
-    for (int r = ns + blockIdx.x * kThreads + threadIdx.x; r < cap; r += gridDim.x * kThreads) perm[r] = -1;
-    // Every XCD takes ONE contiguous eighth of the ranks (ranks run scene by scene): the cell -> voxel-row scatter below is random
-    // inside a scene — rank order is spatial, row order first-come — but touches that scene's ~2 MB of points, codes, first-come
-    // ranks, coordinates and means only, which one 4 MB L2 holds.  With interleaved workgroups every one of those lines went
-    // through all eight L2s (418 MB of HBM traffic per 64-scene launch against ~165 MB of tensors, round 3's PMC).
-    const long long lb = fnp_xcd_block(), nchunk = (ns + kThreads - 1) / kThreads;      // balanced runs of whole 256-rank chunks
-    const int r_begin = (int)(nchunk * lb / gridDim.x) * kThreads, r_end = min(ns, (int)(nchunk * (lb + 1) / gridDim.x) * kThreads);
-    for (int r = r_begin + threadIdx.x; r < r_end; r += kThreads) {
-        CellPts cp;
-        cp.slots = top + (size_t)r * maxp;
-        const int cn = cnt[r];
-        cp.s0 = cp.slots[0];
-        cp.s1 = maxp > 1 ? cp.slots[1] : kSentinel;   // (independent loads: most cells hold one or two points)
-        cp.np = min(cn, maxp);
-        const int p0 = cp.next_above(-1);
-        // the scene of the cell is in its block number: no search in the batch offsets
-        const long long cd = code[p0];
-        int bb, z, y, x;
-        rg_decode(g, cd >> 6, (int)(cd & 63), bb, z, y, x);
-        const int srank = fc[p0] - fc_start[bb];
-        const int id = out_base[bb] + srank;
-        if (srank >= max_voxels || id >= cap) {
-            // dropped by the per-scene cut: no voxel row; its cell goes behind the voxels in the coordinate
-            // list (any order) so that the sparse clear of a persistent grid reaches it
-            perm[r] = -1;
-            if (n_cells) {
-                const int t = out_base[B] + atomicAdd(n_dropped, 1);
-                if (t < cap) reinterpret_cast<int4 *>(coords)[t] = make_int4(bb, z, y, x);
-            }
-            continue;
-        }
-        vox_write_row(pts, C, maxp, cp, p0, r, id, bb, z, y, x, perm, coords, num_points, mean, voxels);
-    }
-}
-
-// POINT form (round 6, default): a thread per POINT in point order; the thread of a cell's FIRST point (fc[i + 1] != fc[i]) writes
+// A thread per POINT in point order; the thread of a cell's FIRST point (fc[i + 1] != fc[i]) writes
 // the voxel.  Point rows, codes, ranks and first-come ranks are then read coalesced, and the voxel rows — first-come order IS point
 // order — are written nearly coalesced: consecutive first points own consecutive rows.  What stays scattered is what is keyed by
 // the cell: its point count, its slot list when it holds more than one point (and those points' rows), and perm[rank].  The cell
@@ -613,15 +561,9 @@ extern "C" int fnp_voxelize(const float *points, int n, const int *batch_offsets
     hipLaunchKernelGGL(vox_scene_kernel, dim3(1), dim3(64), 0, s, batch_offsets, B, n, w.fscan, w.n_first,
                        cfg->max_voxels, cap, w.scene, n_voxels);
     FNP_LAUNCH_CHECK();
-    static const bool cell_form = [] { const char *e = getenv("FNP_VOX_EMIT"); return e && e[0] == 'c'; }();   // (development A/B)
-    if (cell_form)
-        hipLaunchKernelGGL(vox_emit_kernel, dim3(fnp_grid_for(n, kThreads)), dim3(kThreads), 0, s, points, C, maxp,
-                           batch_offsets, B, cfg->max_voxels, g.d, w.code, w.top, (const int *)w.cnt, w.fscan, w.scene, w.n_sorted, n,
-                           g.perm, coords, num_points, mean_feats, voxels, n_cells, w.scene + 2 * (B + 1));
-    else
-        hipLaunchKernelGGL(vox_emit_points_kernel, dim3(pgrid), dim3(kThreads), 0, s, points, n, C, maxp, batch_offsets, B, cfg->max_voxels,
-                           g.d, w.code, (const int *)w.rank, w.top, (const int *)w.cnt, w.fscan, (const int *)w.n_first, w.scene, w.n_sorted, n,
-                           g.perm, coords, num_points, mean_feats, voxels, n_cells, w.scene + 2 * (B + 1));
+    hipLaunchKernelGGL(vox_emit_points_kernel, dim3(pgrid), dim3(kThreads), 0, s, points, n, C, maxp, batch_offsets, B, cfg->max_voxels,
+                       g.d, w.code, (const int *)w.rank, w.top, (const int *)w.cnt, w.fscan, (const int *)w.n_first, w.scene, w.n_sorted, n,
+                       g.perm, coords, num_points, mean_feats, voxels, n_cells, w.scene + 2 * (B + 1));
     FNP_LAUNCH_CHECK();
     return FNP_OK;
 }

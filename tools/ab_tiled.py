@@ -101,7 +101,7 @@ for tag, rb, n_dev in log:
     w = (torch.randn((K, cout, cin), device=dev) * 0.05).to(torch.bfloat16)
     sc, sh = torch.rand(cout, device=dev) + 0.5, torch.randn(cout, device=dev) * 0.1
     resid = torch.randn((rb.cap_out, cout), device=dev).to(torch.bfloat16)
-    # every library restates the table into ITS tile rulebook (a build may change the tile geometry: FNP_TILE32_MB)
+    # every library restates the table into ITS tile rulebook (another commit's build may have another tile geometry)
     trbs = {}
     for name, L in libs.items():
         L.fnp_tile_rulebook_bytes.restype = ctypes.c_longlong
