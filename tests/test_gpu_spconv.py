@@ -696,13 +696,14 @@ def test_dropped_voxels_leave_persistent_grids_clean(cuda):
             assert torch.equal(got[k].indices, want[k].indices) and torch.equal(got[k].features, want[k].features), k
     for g in net.engine()._get_grids(2, cuda):
         assert int(g.bits.count_nonzero()) == 0 and int(g.summary.count_nonzero()) == 0
+        assert g.counters is not None and int(g.counters.count_nonzero()) == 0     # (a word left behind shifts every rank of the next counted build)
 
 
-@pytest.mark.parametrize("B,shape,n", [(2, [41, 300, 300], 40000),      # 23 k summary words: one wave per word
-                                       (3, [41, 1440, 1440], 150000),   # 67 k: 8 words per wave
-                                       (16, [41, 1440, 1440], 400000)]) # 356 k: 64 words per wave
+@pytest.mark.parametrize("B,shape,n", [(2, [41, 300, 300], 40000),      # 2 200 summary words: one wave per word
+                                       (3, [41, 1440, 1440], 150000),   # 66 825: 8 words per wave
+                                       (16, [41, 1440, 1440], 400000)]) # 356 400: 16 words per wave
 def test_rank_grid_prefix_forms_agree(cuda, rng, B, shape, n):
-    """The rank-grid prefix picks its work split (1 / 8 / 64 summary words per wave) from the grid size.  Every
+    """The rank-grid prefix picks its work split (1 / 8 / 16 summary words per wave) from the grid size.  Every
     split must yield the same thing: rank -> row of a clustered coordinate list is a bijection (a 1x1x1 SubM
     rulebook maps every row to itself), and the coordinates emitted in rank order by the strided path (1x1x1,
     stride 1: outputs = inputs) are the input set, each output row fed by the input row with its coordinates."""
