@@ -278,6 +278,51 @@ def prepare_points(points, batch_offsets, batch_size, program, point_cloud_range
     return out
 
 
+def assemble_sweeps(raw, sweep_offsets, scene_sweeps, xform, flags, time_lag, batch_size, center_radius=1.0, out=None):
+    """NuScenesDataset.get_lidar_with_sweeps of a batch on the device, in front of prepare_points (fnp_assemble_sweeps).
+
+    The six arrays of datasets.nuscenes_sweeps.pack_sweeps, as device tensors, for batch_size scenes holding T sweeps in all (a
+    key frame counts as a sweep):
+    raw (R,5) f32: the rows of all sweep files as read from disk, sweep after sweep, scene after scene (column 4 is dropped);
+    sweep_offsets (T+1,) int32: the row range of each sweep; scene_sweeps (B+1,) int32: the sweep range of each scene;
+    xform (T,12) f64: rows 0-2 of each sweep's 4x4 matrix; flags (T,) int32: bit 0 drops the ego returns (|x| < center_radius and
+    |y| < center_radius), bit 1 applies xform (a key frame carries neither, a sweep without a matrix not bit 1);
+    time_lag (T,) f32: the fifth output column.
+    out: a dict returned by an earlier call with the same R and B, whose buffers are reused (a captured graph's static outputs).
+
+    Returns dict(points (R,5) f32: each scene's kept rows in raw order, scene after scene, then PREP_PAD rows; batch_offsets
+    (B+1,) int32; n (1,) int32: the kept count; batch_size; workspace) — points and batch_offsets are what prepare_points,
+    voxelize / forward_points take, over all R rows.  The reference's arithmetic bit for bit.  No host sync, fixed shapes:
+    capturable."""
+    L = _l.load()
+    _l.require_device(raw, sweep_offsets, scene_sweeps, xform, flags, time_lag)
+    assert raw.dtype == torch.float32 and raw.dim() == 2 and raw.shape[1] == 5 and raw.is_contiguous()
+    assert raw.data_ptr() % 16 == 0, "raw: a 16-byte aligned buffer (not a row slice of another tensor)"
+    T = flags.numel()
+    assert sweep_offsets.dtype == torch.int32 and sweep_offsets.numel() == T + 1 and sweep_offsets.is_contiguous()
+    assert scene_sweeps.dtype == torch.int32 and scene_sweeps.numel() == batch_size + 1 and scene_sweeps.is_contiguous()
+    assert xform.dtype == torch.float64 and tuple(xform.shape) == (T, 12) and xform.is_contiguous()
+    assert flags.dtype == torch.int32 and flags.dim() == 1 and flags.is_contiguous()
+    assert time_lag.dtype == torch.float32 and time_lag.numel() == T and time_lag.is_contiguous()
+    n = raw.shape[0]
+    dev = raw.device
+    ws_bytes = int(L.fnp_assemble_sweeps_workspace_bytes(n))
+    _l.check(min(ws_bytes, 0), "fnp_assemble_sweeps_workspace_bytes")
+    if out is None:
+        out = dict(points=torch.empty((n, 5), dtype=torch.float32, device=dev),
+                   workspace=torch.empty((ws_bytes,), dtype=torch.uint8, device=dev))
+        off = torch.empty((batch_size + 1,), dtype=torch.int32, device=dev)
+        out.update(batch_offsets=off, n=off[batch_size:], batch_size=batch_size)
+    else:
+        assert out["points"].shape == (n, 5) and out["batch_offsets"].numel() == batch_size + 1 and out["workspace"].numel() >= ws_bytes
+    rc = L.fnp_assemble_sweeps(_l.ptr(raw) if n else None, n, _l.ptr(sweep_offsets), T, _l.ptr(scene_sweeps), batch_size,
+                               _l.ptr(xform) if T else None, _l.ptr(flags) if T else None, _l.ptr(time_lag) if T else None,
+                               float(center_radius), PREP_PAD, _l.ptr(out["workspace"]), out["workspace"].numel(),
+                               _l.ptr(out["points"]) if n else None, _l.ptr(out["batch_offsets"]), _l.stream())
+    _l.check(rc, "fnp_assemble_sweeps")
+    return out
+
+
 def voxelize(points, batch_offsets, batch_size, cfg, grid=None, want_voxels=False, workspace=None):
     """points (N,C) f32 device, batch_offsets (B+1,) int32 device.
 

@@ -115,6 +115,46 @@ def make_sweeps_batch(seeds, sweeps=10):
     return np.concatenate(scenes, 0), off
 
 
+def make_raw_sweeps(seed, sweeps=10):
+    """The 10-sweep sample BEFORE assembly: what get_lidar_with_sweeps reads for one sample, as a scene of
+    datasets.nuscenes_sweeps.pack_sweeps — a list of (raw (n, 5) f32 [x, y, z, intensity, ring] as a sweep file holds it,
+    matrix (4, 4) f64 or None, time_lag, is_key), the key frame first.  Sweep j > 0 is the seeded static world seen from the ego
+    pose j steps back (~0.5 m apart, a yaw of a few mrad, pitch and roll terms of a mrad): raw = R_j^T (p - t_j) of ~93 % of the
+    key frame's returns, matrix = [R_j t_j], time lag 0.05 j.  Every sweep also holds ~1.5 % returns from the ego vehicle itself
+    (|x|, |y| < 1: what remove_ego_points drops; the key frame keeps its own).  The last sweep is the key frame's file again with
+    no matrix and lag 0, as the info builder pads a sample that has too few sweeps."""
+    rng = np.random.default_rng(77_000 + seed)
+    world = make_scene(seed)
+
+    def with_ego(xyz, intensity):
+        k = max(1, int(0.015 * xyz.shape[0]))
+        raw = np.empty((xyz.shape[0] + k, 5), np.float32)
+        raw[:-k, :3], raw[:-k, 3] = xyz, intensity
+        raw[-k:, 0:2] = rng.uniform(-0.98, 0.98, (k, 2))
+        raw[-k:, 2] = rng.uniform(-1.6, -0.4, k)
+        raw[-k:, 3] = rng.uniform(0.0, 30.0, k)
+        raw[:, 4] = rng.integers(0, 32, raw.shape[0])
+        return raw[rng.permutation(raw.shape[0])]     # (the ego returns lie anywhere in the firing order)
+
+    key = with_ego(world[:, :3], world[:, 3])
+    scene = [(key, None, 0.0, True)]
+    for j in range(1, sweeps):
+        if j == sweeps - 1 and sweeps > 2:
+            scene.append((key.copy(), None, 0.0, False))
+            continue
+        yaw, pitch, roll = 0.004 * j + rng.normal(0, 1e-3), rng.normal(0, 1e-3), rng.normal(0, 1e-3)
+        cz, sz, cy, sy, cx, sx = np.cos(yaw), np.sin(yaw), np.cos(pitch), np.sin(pitch), np.cos(roll), np.sin(roll)
+        R = (np.array([[cz, -sz, 0], [sz, cz, 0], [0, 0, 1.0]]) @ np.array([[cy, 0, sy], [0, 1.0, 0], [-sy, 0, cy]])
+             @ np.array([[1.0, 0, 0], [0, cx, -sx], [0, sx, cx]]))
+        t = np.array([-(0.5 * j + 0.013 * j * j), -0.07 * j, rng.normal(0, 0.01)])
+        M = np.eye(4)
+        M[:3, :3], M[:3, 3] = R, t
+        seen = world[rng.random(world.shape[0]) < 0.93]
+        xyz = (seen[:, :3].astype(np.float64) - t) @ R          # rows of R^T (p - t)
+        scene.append((with_ego(xyz.astype(np.float32), seen[:, 3]), M, 0.05 * j, False))
+    return scene
+
+
 def make_batch(seeds):
     """Concatenate scenes: points (N,5) f32, batch_offsets (B+1,) int32."""
     scenes = [make_scene(s) for s in seeds]

@@ -296,6 +296,33 @@ int fnp_prepare_points_cut_window(const float *points, int64_t n_points, int num
                                   void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets, fnp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Multi-sweep assembly in front of fnp_prepare_points — replaces, on the device, NuScenesDataset.get_lidar_with_sweeps and
+ * get_sweep (pcdet/datasets/nuscenes/nuscenes_dataset.py:88-121), which the reference runs in numpy inside DataLoader workers.
+ * ------------------------------------------------------------------------------------------ */
+enum { FNP_SWEEP_DROP_EGO = 1, FNP_SWEEP_TRANSFORM = 2 };
+
+int64_t fnp_assemble_sweeps_workspace_bytes(int64_t n_rows);
+
+/* A batch of B scenes holding T sweeps in all (every key frame counts as a sweep).  All arrays on the device:
+ * raw (R, 5) f32, 16-byte aligned: the rows of all sweep files as read from disk, sweep after sweep, scene after scene
+ *   (column 4, the ring index, is dropped, as the reference's [:, :4] does);
+ * sweep_offsets (T+1,) int32: sweep t owns rows [sweep_offsets[t], sweep_offsets[t+1]);
+ * scene_sweeps (B+1,) int32: scene b owns sweeps [scene_sweeps[b], scene_sweeps[b+1]);
+ * xform (T, 12) f64: rows 0-2 of the sweep's 4x4 matrix, row-major;  flags (T,) int32: FNP_SWEEP_DROP_EGO drops the rows with
+ *   |x| < center_radius && |y| < center_radius (both strict, the raw f32 values against the f64 radius), FNP_SWEEP_TRANSFORM
+ *   moves x, y, z by xform: fma(m2, z, fma(m1, y, m0*x)) + m3 in f64 (the accumulation of BLAS's dgemm, which numpy's dot
+ *   runs for the reference), rounded to f32 once
+ *   (a sweep without a matrix does not carry the flag: an identity would turn -0.0 into +0.0);  a key frame carries neither;
+ * time_lag (T,) f32: the fifth output column of the sweep's rows.  Intensity passes through.
+ * Outputs, the contract of fnp_prepare_points: out_points (R, 5) f32: every scene's kept rows in raw order, scene after scene,
+ *   then rows [kept, R) = pad in every column; out_offsets (B+1,) int32: the scene offsets, out_offsets[B] the kept count.
+ * No atomics, no host synchronisation, fixed launch sequence for fixed shapes: capturable. */
+int fnp_assemble_sweeps(const float *raw, int64_t n_rows, const int *sweep_offsets, int num_sweeps, const int *scene_sweeps,
+                        int batch_size, const double *xform, const int *flags, const float *time_lag, double center_radius,
+                        float pad, void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets,
+                        fnp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * Rulebooks — replace spconv's indice-pair generation for SubMConv3d / SparseConv3d
  * (call sites pcdet/models/backbones_3d/spconv_backbone.py:12-17,39-46,193-234).
  * Output-stationary layout: nbr[k*cap + o] = input row feeding output row o through kernel
