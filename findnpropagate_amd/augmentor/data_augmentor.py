@@ -29,6 +29,15 @@ pending cut (the rows below prep_cut_from, and the rows inside no cut box): host
 the np.random draws and the pasted rows are the host mode's.  It then records data_dict['prep_cut_to'], the rows in front of
 the first pasted row, so that the device cut spares the pasted rows; stack_cut_boxes(..., cut_to_list) makes the 4-tuple cut
 of sparse.prepare_points.  A deferred unknowns_copy_paste after a recorded world op raises ValueError.
+RAW SCENES.  A deferred DataAugmentor also takes a scene that has no 'points' but data_dict['raw_sweeps'], a scene of
+datasets.nuscenes_sweeps.pack_sweeps whose rows the device will assemble (sparse.assemble_sweeps): gt_sampling records its object
+rows in data_dict['prep_lead_rows'] instead of putting them in front of rows that do not exist yet, unknowns_copy_paste obtains the
+rows inside its copy boxes from the provider data_dict['scene_rows'] (nuscenes_sweeps.HostSceneRows, the default, or
+DeviceSceneRows) and records the pasted rows in data_dict['prep_tail_rows']; the queue logic, the np.random draws, the boxes and
+the programme are those of the host mode on the assembled scene.  forward is forward_head then forward_tail: forward_head runs the
+entries in front of the first one that needs scene rows (file reads, gt_sampling, the two load_*: a DataLoader worker can run it),
+forward_tail the rest and the epilogue, in the process that owns the device — and with it the copy-paste queue, which then lives
+in that one process.  The order of work for a batch is in INTEGRATION.md.
 Any other augmentor (random_local_*, frustum dropout, image ops) raises NotImplementedError naming itself, unless
 DISABLE_AUG_LIST lists it.
 """
@@ -38,13 +47,18 @@ import numpy as np
 import torch
 
 from . import database_sampler
-from .pseudo_loader import PseudoLoader, rotate_points_along_z
+from .pseudo_loader import TAIL_ROWS_KEY, PseudoLoader, rotate_points_along_z
 
 OP_NONE, OP_FLIP_X, OP_FLIP_Y, OP_ROTATE, OP_SCALE, OP_TRANSLATE = range(6)
 MAX_STEPS = 6   # FNP_PREP_MAX_STEPS (include/fnp.h)
 PROGRAM_KEY = 'prep_program'
 CUT_TO_KEY = 'prep_cut_to'
 CUT_TO_END = 0x7fffffff   # a cut_to that reaches the end of the scene
+RAW_SWEEPS_KEY = database_sampler.RAW_SWEEPS_KEY
+LEAD_ROWS_KEY = database_sampler.LEAD_ROWS_KEY
+SCENE_ROWS_KEY = 'scene_rows'
+COPY_STATE_KEY = 'prep_copy_state'   # forward_head -> forward_tail: the loader's copy boxes of this frame
+NEEDS_SCENE_ROWS = ('unknowns_copy_paste',)
 SUPPORTED = ('gt_sampling', 'load_frustum_pseudos', 'load_selftrain_pseudos', 'unknowns_copy_paste', 'random_world_flip',
              'random_world_rotation', 'random_world_scaling', 'random_world_translation')
 
@@ -168,6 +182,7 @@ class DataAugmentor(object):
 
     def _build_queue(self, augmentor_configs):
         self.data_augmentor_queue = []
+        self.queue_names = []
         is_list = isinstance(augmentor_configs, list)
         cfg_list = augmentor_configs if is_list else _get(augmentor_configs, 'AUG_CONFIG_LIST')
         disabled = [] if is_list else (_get(augmentor_configs, 'DISABLE_AUG_LIST', None) or [])
@@ -178,6 +193,7 @@ class DataAugmentor(object):
             if name not in SUPPORTED:
                 raise NotImplementedError(f"DataAugmentor.{name} is not implemented in this build (list it in DISABLE_AUG_LIST)")
             self.data_augmentor_queue.append(getattr(self, name)(config=cur_cfg))
+            self.queue_names.append(name)
 
     def disable_augmentation(self, augmentor_configs):
         self._build_queue(augmentor_configs)
@@ -241,6 +257,13 @@ class DataAugmentor(object):
         if self.deferred and PROGRAM_KEY in data_dict:
             raise ValueError("a deferred unknowns_copy_paste must come before the world ops: the rows it appends are not "
                              "transformed, and the program applies to every row")
+        if self.deferred and 'points' not in data_dict and RAW_SWEEPS_KEY in data_dict:
+            provider = data_dict.get(SCENE_ROWS_KEY)
+            if provider is None:   # no device in this process: the host assembly answers
+                from ..datasets.nuscenes_sweeps import HostSceneRows
+                provider = HostSceneRows(data_dict[RAW_SWEEPS_KEY], lead=data_dict.get(LEAD_ROWS_KEY))
+            cut_boxes = data_dict.get(database_sampler.CUT_BOXES_KEY)
+            return self.pseudo_loader.copy_and_paste(data_dict, rows=lambda boxes7: provider(boxes7, cut_boxes))
         if not (self.deferred and database_sampler.CUT_BOXES_KEY in data_dict):
             return self.pseudo_loader.copy_and_paste(data_dict)
         n_scene = int(data_dict['points'].shape[0])
@@ -249,6 +272,12 @@ class DataAugmentor(object):
         data_dict = self.pseudo_loader.copy_and_paste(data_dict, cut=cut)
         data_dict[CUT_TO_KEY] = n_scene
         return data_dict
+
+    def _points(self, data_dict):
+        """the scene's points; None for a raw scene of the deferred mode, whose rows are not assembled yet"""
+        if self.deferred and 'points' not in data_dict and RAW_SWEEPS_KEY in data_dict:
+            return None
+        return data_dict['points']
 
     def _record(self, data_dict, op, a=0.0, b=0.0, c=0.0):
         """deferred mode: append one step to the scene's program"""
@@ -262,7 +291,7 @@ class DataAugmentor(object):
     def random_world_flip(self, data_dict=None, config=None):
         if data_dict is None:
             return partial(self.random_world_flip, config=config)
-        gt_boxes, points = data_dict['gt_boxes'], data_dict['points']
+        gt_boxes, points = data_dict['gt_boxes'], self._points(data_dict)
         for cur_axis in config['ALONG_AXIS_LIST']:
             assert cur_axis in ['x', 'y']
             enable = np.random.choice([False, True], replace=False, p=[0.5, 0.5])
@@ -288,7 +317,8 @@ class DataAugmentor(object):
                         pb[:, 6] = -(pb[:, 6] + np.pi)
                 data_dict['pseudo_boxes'] = pb
         data_dict['gt_boxes'] = gt_boxes
-        data_dict['points'] = points
+        if points is not None:
+            data_dict['points'] = points
         return data_dict
 
     def random_world_rotation(self, data_dict=None, config=None):
@@ -298,7 +328,7 @@ class DataAugmentor(object):
         if not isinstance(rot_range, list):
             rot_range = [-rot_range, rot_range]
         noise_rot = np.random.uniform(rot_range[0], rot_range[1])
-        points = data_dict['points']
+        points = self._points(data_dict)
         if self.deferred:
             self._record(data_dict, OP_ROTATE, *rotation_cos_sin(noise_rot))
         else:
@@ -313,7 +343,8 @@ class DataAugmentor(object):
             pb[:, 6] += noise_rot
             data_dict['pseudo_boxes'] = pb
         data_dict['gt_boxes'] = gt_boxes
-        data_dict['points'] = points
+        if points is not None:
+            data_dict['points'] = points
         data_dict['noise_rot'] = noise_rot
         return data_dict
 
@@ -325,7 +356,7 @@ class DataAugmentor(object):
             # the reference returns two values here where its caller unpacks three (augmentor_utils.py:119-120)
             raise ValueError("random_world_scaling: WORLD_SCALE_RANGE narrower than 1e-3")
         noise_scale = np.random.uniform(scale_range[0], scale_range[1])
-        gt_boxes, points = data_dict['gt_boxes'], data_dict['points']
+        gt_boxes, points = data_dict['gt_boxes'], self._points(data_dict)
         if self.deferred:
             self._record(data_dict, OP_SCALE, np.float32(noise_scale))
         else:
@@ -341,7 +372,8 @@ class DataAugmentor(object):
             pb[:, :6] *= noise_scale
             data_dict['pseudo_boxes'] = pb
         data_dict['gt_boxes'] = gt_boxes
-        data_dict['points'] = points
+        if points is not None:
+            data_dict['points'] = points
         data_dict['noise_scale'] = noise_scale
         return data_dict
 
@@ -352,7 +384,7 @@ class DataAugmentor(object):
         assert len(std) == 3
         draws = [np.random.normal(0, std[0], 1), np.random.normal(0, std[1], 1), np.random.normal(0, std[2], 1)]
         noise_translate = np.array(draws, dtype=np.float32).T   # (1, 3) f32
-        gt_boxes, points = data_dict['gt_boxes'], data_dict['points']
+        gt_boxes, points = data_dict['gt_boxes'], self._points(data_dict)
         if self.deferred:
             self._record(data_dict, OP_TRANSLATE, *noise_translate[0])
         else:
@@ -363,13 +395,33 @@ class DataAugmentor(object):
         if 'roi_boxes' in data_dict.keys():
             data_dict['roi_boxes'][:, :3] += noise_translate
         data_dict['gt_boxes'] = gt_boxes
-        data_dict['points'] = points
+        if points is not None:
+            data_dict['points'] = points
         data_dict['noise_translate'] = noise_translate
         return data_dict
 
-    def forward(self, data_dict):
-        """Run the queue, then the reference's epilogue (data_augmentor.py:374-398)."""
-        for cur_augmentor in self.data_augmentor_queue:
+    def _split(self):
+        """index of the first queue entry that needs the scene rows (the queue's length when none does)"""
+        names = getattr(self, 'queue_names', None) or []
+        return next((k for k, n in enumerate(names) if n in NEEDS_SCENE_ROWS), len(self.data_augmentor_queue))
+
+    def forward_head(self, data_dict):
+        """The entries in front of the first one that needs scene rows: file reads, gt_sampling, the two load_*.  Needs no
+        device and no assembled rows; what the loader keeps of this frame for unknowns_copy_paste travels in the data_dict."""
+        for cur_augmentor in self.data_augmentor_queue[:self._split()]:
+            data_dict = cur_augmentor(data_dict=data_dict)
+        loader = getattr(self, 'pseudo_loader', None)
+        if loader is not None:
+            data_dict[COPY_STATE_KEY] = (loader.copy_boxes, loader.copy_scores, loader.pseudo_types)
+        return data_dict
+
+    def forward_tail(self, data_dict):
+        """The rest of the queue, then the reference's epilogue (data_augmentor.py:374-398): in the process that owns the
+        copy-paste queue (and, for raw scenes answered by DeviceSceneRows, the device)."""
+        state = data_dict.pop(COPY_STATE_KEY, None)
+        if state is not None:
+            self.pseudo_loader.copy_boxes, self.pseudo_loader.copy_scores, self.pseudo_loader.pseudo_types = state
+        for cur_augmentor in self.data_augmentor_queue[self._split():]:
             data_dict = cur_augmentor(data_dict=data_dict)
         data_dict.pop('pseudo_scores', None)
         data_dict['gt_boxes'][:, 6] = limit_period(data_dict['gt_boxes'][:, 6], offset=0.5, period=2 * np.pi)
@@ -381,3 +433,7 @@ class DataAugmentor(object):
             if 'gt_boxes2d' in data_dict:
                 data_dict['gt_boxes2d'] = data_dict['gt_boxes2d'][gt_boxes_mask]
         return data_dict
+
+    def forward(self, data_dict):
+        """Run the queue, then the reference's epilogue (data_augmentor.py:374-398): forward_head, then forward_tail."""
+        return self.forward_tail(self.forward_head(data_dict))

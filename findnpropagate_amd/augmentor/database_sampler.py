@@ -13,7 +13,10 @@ add_sampled_boxes_to_scene cuts the scene points that lie inside the sampled box
   deferred  (deferred=True) the object rows are put in front of the scene rows untested, and the cut is recorded for
             sparse.prepare_points: data_dict['prep_cut_boxes'] (M, 7) f32, the enlarged boxes as the host mode tests them, and
             data_dict['prep_cut_from'], the number of leading object rows (never cut).  The collate stacks them with
-            data_augmentor.stack_cut_boxes.
+            data_augmentor.stack_cut_boxes.  A scene without data_dict['points'] and with data_dict['raw_sweeps'] (a
+            datasets.nuscenes_sweeps.pack_sweeps scene that the device assembles) has no rows to put the object rows in front
+            of: they are recorded in data_dict['prep_lead_rows'] ((n, 5) f32; (0, 5) when nothing is sampled) and travel as a
+            finished-row sweep in front of the scene's sweeps (pack_sweeps(lead=)), whose window yields prep_cut_from on the card.
 USE_ROAD_PLANE, IMG_AUG_TYPE, USE_SHARED_MEMORY, a true DATABASE_WITH_FAKELIDAR and the BACKUP_DB_INFO fallback (none of them in
 the nuScenes configs) raise NotImplementedError naming the key.
 """
@@ -27,6 +30,9 @@ from ..iou3d_nms import iou3d_nms_utils
 
 CUT_BOXES_KEY = 'prep_cut_boxes'
 CUT_FROM_KEY = 'prep_cut_from'
+LEAD_ROWS_KEY = 'prep_lead_rows'
+RAW_SWEEPS_KEY = 'raw_sweeps'
+RAW_FEATURES = 5   # the columns of an assembled row: x, y, z, intensity, time lag
 
 
 def _get(config, key, default=None):
@@ -174,7 +180,8 @@ class DataBaseSampler(object):
         gt_boxes_mask = data_dict['gt_boxes_mask']
         gt_boxes = data_dict['gt_boxes'][gt_boxes_mask]
         gt_names = data_dict['gt_names'][gt_boxes_mask]
-        points = data_dict['points']
+        raw = self.deferred and 'points' not in data_dict and RAW_SWEEPS_KEY in data_dict
+        points = np.zeros((0, RAW_FEATURES), np.float32) if raw else data_dict['points']
 
         obj_points = np.concatenate([self._object_points(info) for info in total_valid_sampled_dict], axis=0)
         sampled_gt_names = np.array([x['name'] for x in total_valid_sampled_dict])
@@ -199,12 +206,14 @@ class DataBaseSampler(object):
         else:   # (remove_points_in_boxes3d hands back its f32 copy of the points)
             points = np.asarray(points, np.float32)
             points = points[points_outside_boxes(points[:, 0:3], cut_records(large_sampled_gt_boxes))]
-        points = np.concatenate([obj_rows, points], axis=0)
         gt_names = np.concatenate([gt_names, sampled_gt_names], axis=0)
         gt_boxes = np.concatenate([gt_boxes, sampled_gt_boxes], axis=0)
         data_dict['gt_boxes'] = gt_boxes
         data_dict['gt_names'] = gt_names
-        data_dict['points'] = points
+        if raw:
+            data_dict[LEAD_ROWS_KEY] = np.ascontiguousarray(obj_rows, np.float32)
+        else:
+            data_dict['points'] = np.concatenate([obj_rows, points], axis=0)
         return data_dict
 
     def __call__(self, data_dict):
@@ -215,6 +224,8 @@ class DataBaseSampler(object):
         if self.deferred:   # nothing to cut unless something is sampled
             data_dict[CUT_BOXES_KEY] = np.zeros((0, 7), np.float32)
             data_dict[CUT_FROM_KEY] = 0
+            if 'points' not in data_dict and RAW_SWEEPS_KEY in data_dict:
+                data_dict[LEAD_ROWS_KEY] = np.zeros((0, RAW_FEATURES), np.float32)
 
         for class_name, sample_group in self.sample_groups.items():
             if self.limit_whole_scene:

@@ -113,6 +113,7 @@ def points_in_boxes_compact(points, boxes3d, cut=None):
 # including the ORDER in which np.random is consumed, so that a seeded run reproduces the reference's samples — with
 # the per-box Python loops replaced by array operations where the order of side effects allows it.
 # ------------------------------------------------------------------------------------------------------------------
+TAIL_ROWS_KEY = 'prep_tail_rows'
 ALL_CLASS_NAMES = ['car', 'truck', 'construction_vehicle', 'bus', 'trailer',
                    'barrier', 'motorcycle', 'bicycle', 'pedestrian', 'traffic_cone']
 
@@ -237,21 +238,33 @@ class PseudoSampler(object):
     def points_in_boxes(self, points, boxes3d):
         return points_in_boxes(points, boxes3d)
 
-    def __call__(self, batch_dict, pseudo_boxes, pseudo_scores, gt_boxes, sample_buffer_num=5, fix_cp=None, cut=None):
+    def __call__(self, batch_dict, pseudo_boxes, pseudo_scores, gt_boxes, sample_buffer_num=5, fix_cp=None, cut=None, rows=None):
         """cut: None, or gt_sampling's pending cut (records, cut_from, cut_to) of a deferred DataAugmentor: the queue is fed as
-        if the rows it drops were gone already (points_in_boxes_compact); the pasted rows still follow every row."""
+        if the rows it drops were gone already (points_in_boxes_compact); the pasted rows still follow every row.
+        rows: None, or the scene-row provider of a scene that has no batch_dict['points'] (a deferred DataAugmentor on raw sweeps):
+        rows(boxes (T, 7)) -> (counts (T,), the raw rows inside, box after box in row order (K, 5) f32), the pending cut already
+        applied; the pasted rows are then recorded in batch_dict['prep_tail_rows'] ((n, 5) f32) instead of appended."""
         self.calc_seen_per_class(pseudo_boxes, gt_boxes)
         in_queue = {l: len(q) for l, q in self.unknown_queue.items()}
         num_scaled = max(int(gt_boxes.shape[0] * self.known_to_unknown_ratio), pseudo_boxes.shape[0])
         num_proposals = num_scaled + (sample_buffer_num if fix_cp is None else fix_cp)
-        cur_points = batch_dict['points'].copy()
+        cur_points = batch_dict['points'].copy() if rows is None else None
+        if rows is not None:
+            batch_dict[TAIL_ROWS_KEY] = np.zeros((0, 5), np.float32)
         if pseudo_boxes.size == 0:
             return pseudo_boxes, np.zeros((0), dtype=bool)
         gt_plus_ego = torch.cat((torch.tensor(gt_boxes.copy(), dtype=torch.float32)[:, :7], self.ego_vehicle), dim=0)
-        assert cur_points.shape[-1] == 5
-        n_in, idx, _ = points_in_boxes_compact(cur_points, pseudo_boxes[:, :7], cut=cut)
+        if rows is None:
+            assert cur_points.shape[-1] == 5
+            n_in, idx, _ = points_in_boxes_compact(cur_points, pseudo_boxes[:, :7], cut=cut)
+            inside = lambda lo, hi: cur_points[idx[lo:hi]]
+        else:
+            n_in, raw_rows = rows(np.ascontiguousarray(pseudo_boxes[:, :7], np.float32))
+            n_in = np.asarray(n_in, np.int64)
+            assert raw_rows.shape == (int(n_in.sum()), 5)
+            inside = lambda lo, hi: raw_rows[lo:hi]
         first = np.concatenate([[0], np.cumsum(n_in)])
-        rel_pts = lambda i: _box_frame(cur_points[idx[first[i]:first[i + 1]]], pseudo_boxes[i])
+        rel_pts = lambda i: _box_frame(inside(first[i], first[i + 1]), pseudo_boxes[i])
         order = np.argsort(-n_in, axis=0) if self.queue_metric == 'num_pts' else np.argsort(-pseudo_scores, axis=0)
         max_per_unknown = gt_boxes.shape[0] / max(len(self.known_class_labels), 1)
         seen = {l: 0 for l in self.unknown_class_labels}
@@ -300,7 +313,10 @@ class PseudoSampler(object):
             pasted[lbl] += 1
             pos += 1
             extra_points.append(pts)
-        batch_dict['points'] = np.concatenate(extra_points, axis=0)
+        if rows is None:
+            batch_dict['points'] = np.concatenate(extra_points, axis=0)
+        elif len(extra_points) > 1:
+            batch_dict[TAIL_ROWS_KEY] = np.ascontiguousarray(np.concatenate(extra_points[1:], axis=0), np.float32)
         return out, mask
 
 
@@ -417,10 +433,11 @@ class PseudoLoader(object):
         batch_dict['pseudo_samples_mask'] = np.zeros((len(boxes),), dtype=bool)
         return batch_dict
 
-    def copy_and_paste(self, batch_dict, cut=None):
-        """cut: gt_sampling's pending cut (PseudoSampler.__call__), None in the reference's order of work"""
+    def copy_and_paste(self, batch_dict, cut=None, rows=None):
+        """cut: gt_sampling's pending cut (PseudoSampler.__call__), None in the reference's order of work; rows: the scene-row
+        provider of a scene without batch_dict['points'] (PseudoSampler.__call__)"""
         boxes, mask = self.sampler(batch_dict, self.copy_boxes, self.copy_scores, batch_dict['gt_boxes'], fix_cp=self.fix_cp,
-                                   cut=cut)
+                                   cut=cut, rows=rows)
         boxes, non_empty = remove_empty(boxes)
         mask = mask[non_empty]
         if self.copy_st_only:                   # the frustum pseudos were kept out of the sampler: add them back

@@ -14,6 +14,12 @@
 //                                                                                                           [sweeps_emit]
 // No atomics, no host synchronisation; every row count is read from device memory.
 //
+// fnp_assemble_sweeps_window runs the same four launches on the <true> instantiations of the three kernels: a sweep flagged
+// SWEEP_FINISHED (gt_sampling's object rows in front of a scene, unknowns_copy_paste's pasted rows behind it) keeps every row and
+// leaves as it came, five columns bit for bit; sweeps_offsets also counts, per scene, the kept rows in front of the first and the
+// end row of the scene's cut window — the cut_from / cut_to of fnp_prepare_points_cut_window, which the host cannot know once the
+// ego returns are dropped here.  fnp_assemble_sweeps keeps the <false> instantiations: the code it had.
+//
 // ROWS OF 20 BYTES.  A thread that loads its own row issues dword loads 20 bytes apart: five instructions that each touch ten
 // 128-byte lines.  Both passes instead read the workgroup's 256 rows as what they are, 5120 contiguous bytes, 16 bytes per lane
 // (320 chunks, 16-byte aligned because the base is and 5120 is a multiple of 16), into LDS; a thread then reads its row at a
@@ -32,7 +38,7 @@ constexpr int kCols = 5;                          // a raw row: x, y, z, intensi
 constexpr int kTileWords = kThreads * kCols;      // 1280
 constexpr int kTileChunks = kTileWords / 4;       // 320
 
-enum { SWEEP_DROP_EGO = 1, SWEEP_TRANSFORM = 2 };
+enum { SWEEP_DROP_EGO = 1, SWEEP_TRANSFORM = 2, SWEEP_FINISHED = 4 };
 
 struct SweepWs {
     unsigned long long *mask;   // (G*4) ballot of kept rows per wave
@@ -94,6 +100,8 @@ __device__ __forceinline__ int sweep_of_wave(const int *__restrict__ off, int T,
 // remove_ego_points: both comparisons strict, on the raw f32 values against the f64 radius
 __device__ __forceinline__ bool ego_return(float x, float y, double r) { return fabs((double)x) < r && fabs((double)y) < r; }
 
+// kFinished (fnp_assemble_sweeps_window): a sweep with SWEEP_FINISHED holds finished rows, which are never ego returns
+template <bool kFinished>
 __global__ __launch_bounds__(kThreads) void sweeps_mark_kernel(const float *__restrict__ raw, int n, const int *__restrict__ off, int T,
                                                                const int *__restrict__ flags, double radius,
                                                                unsigned long long *__restrict__ mask, int *__restrict__ cnt) {
@@ -105,7 +113,9 @@ __global__ __launch_bounds__(kThreads) void sweeps_mark_kernel(const float *__re
     bool keep = false;
     if (i < n && i >= off[0] && i < off[T]) {
         const int t = sweep_of_wave(off, T, (int)i);
-        keep = !((flags[t] & SWEEP_DROP_EGO) && ego_return(tile[threadIdx.x * kCols], tile[threadIdx.x * kCols + 1], radius));
+        const int f = flags[t];
+        const bool drop = (f & SWEEP_DROP_EGO) && !(kFinished && (f & SWEEP_FINISHED));
+        keep = !(drop && ego_return(tile[threadIdx.x * kCols], tile[threadIdx.x * kCols + 1], radius));
     }
     const unsigned long long bal = __ballot(keep);
     const int wave = threadIdx.x >> 6;
@@ -126,11 +136,15 @@ __device__ __forceinline__ int kept_before(const unsigned long long *__restrict_
     return k + __popcll(mask[(size_t)blk * kWaves + w] & ((1ull << lane) - 1ull));
 }
 
-// scene offsets: o_b = kept rows in front of the first row of scene b's first sweep (thread per entry; o_B = every kept row)
+// scene offsets: o_b = kept rows in front of the first row of scene b's first sweep (thread per entry; o_B = every kept row).
+// kWindow: also out_window[b] = {kept rows of scene b in front of the first row of sweep window_sweeps[b][0], in front of the first
+// row of sweep window_sweeps[b][1]}, both sweep indices clamped into the scene's own sweep range, both counts relative to o_b.
+template <bool kWindow>
 __global__ __launch_bounds__(kThreads) void sweeps_offsets_kernel(const int *__restrict__ off, int T, const int *__restrict__ scene_sweeps, int B,
                                                                   int n, const unsigned long long *__restrict__ mask,
                                                                   const int *__restrict__ base, const int *__restrict__ total,
-                                                                  int *__restrict__ out_off) {
+                                                                  int *__restrict__ out_off, const int *__restrict__ window_sweeps,
+                                                                  int *__restrict__ out_window) {
     const int b = blockIdx.x * kThreads + threadIdx.x;
     if (b > B) return;
     const int tot = *total;
@@ -138,7 +152,19 @@ __global__ __launch_bounds__(kThreads) void sweeps_offsets_kernel(const int *__r
     t = t < 0 ? 0 : (t > T ? T : t);
     int i = off[t];
     i = i < 0 ? 0 : i;
-    out_off[b] = b == B ? tot : kept_before(mask, base, tot, n, i);
+    const int o = b == B ? tot : kept_before(mask, base, tot, n, i);
+    out_off[b] = o;
+    if (kWindow && b < B) {
+        int t1 = scene_sweeps[b + 1];
+        t1 = t1 < t ? t : (t1 > T ? T : t1);
+        for (int k = 0; k < 2; ++k) {
+            int w = window_sweeps[2 * b + k];
+            w = w < t ? t : (w > t1 ? t1 : w);
+            int j = off[w];
+            j = j < i ? i : j;
+            out_window[2 * b + k] = kept_before(mask, base, tot, n, j) - o;
+        }
+    }
 }
 
 // One output coordinate of get_sweep's transform_matrix.dot(vstack((xyz, ones))), stored into the f32 array: x, y, z widened to
@@ -153,6 +179,8 @@ __device__ __forceinline__ float xform_row(const double *__restrict__ m, double 
     return __double2float_rn(s);
 }
 
+// kFinished: a sweep with SWEEP_FINISHED leaves as it came, all five columns bit for bit (no transform, its own column 4)
+template <bool kFinished>
 __global__ __launch_bounds__(kThreads) void sweeps_emit_kernel(const float *__restrict__ raw, int n, const int *__restrict__ off, int T,
                                                                const double *__restrict__ xform, const int *__restrict__ flags,
                                                                const float *__restrict__ time_lag, const unsigned long long *__restrict__ mask,
@@ -174,6 +202,11 @@ __global__ __launch_bounds__(kThreads) void sweeps_emit_kernel(const float *__re
     const int slot = kept_before(mask, base, total, n, (int)i);
     if (slot < 0 || slot >= total) return;
     const float *p = tile + threadIdx.x * kCols;
+    float *q = out + (size_t)slot * kCols;
+    if (kFinished && (flags[t] & SWEEP_FINISHED)) {
+        for (int c = 0; c < kCols; ++c) q[c] = p[c];
+        return;
+    }
     float x = p[0], y = p[1], z = p[2];
     if (flags[t] & SWEEP_TRANSFORM) {                     // (never an identity for "no matrix": 1*x + 0 + 0 + 0 loses the sign of -0.0)
         const double *m = xform + (size_t)t * 12;
@@ -182,7 +215,6 @@ __global__ __launch_bounds__(kThreads) void sweeps_emit_kernel(const float *__re
         y = xform_row(m + 4, dx, dy, dz);
         z = xform_row(m + 8, dx, dy, dz);
     }
-    float *q = out + (size_t)slot * kCols;
     q[0] = x;
     q[1] = y;
     q[2] = z;
@@ -198,14 +230,20 @@ extern "C" int64_t fnp_assemble_sweeps_workspace_bytes(int64_t n_rows) {
     return carve(w, nullptr, n_rows > 0 ? n_rows : 1);
 }
 
-extern "C" int fnp_assemble_sweeps(const float *raw, int64_t n_rows, const int *sweep_offsets, int num_sweeps, const int *scene_sweeps,
-                                   int batch_size, const double *xform, const int *flags, const float *time_lag, double center_radius,
-                                   float pad, void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets,
-                                   fnp_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
+namespace {
+
+template <bool kWindow>
+int assemble(const float *raw, int64_t n_rows, const int *sweep_offsets, int num_sweeps, const int *scene_sweeps, int batch_size,
+             const double *xform, const int *flags, const float *time_lag, double center_radius, float pad, void *workspace,
+             int64_t workspace_bytes, float *out_points, int *out_offsets, const int *window_sweeps, int *out_window, hipStream_t s) {
     if (n_rows < 0 || n_rows > 0x7fffffffll || num_sweeps < 0 || batch_size <= 0 || !scene_sweeps || !out_offsets) return FNP_ERR_ARG;
+    if (kWindow && (!window_sweeps || !out_window)) return FNP_ERR_ARG;
     const int n = (int)n_rows, B = batch_size, T = num_sweeps;
     if (n == 0) {   // no rows: every scene keeps nothing
+        if (kWindow) {
+            const int rc = fnp_fill_words(out_window, 2ll * B, 0u, s);
+            if (rc) return rc;
+        }
         return fnp_fill_words(out_offsets, (long long)B + 1, 0u, s);
     }
     if (!raw || !sweep_offsets || !workspace || !out_points) return FNP_ERR_ARG;
@@ -215,15 +253,37 @@ extern "C" int fnp_assemble_sweeps(const float *raw, int64_t n_rows, const int *
     if (carve(w, (char *)workspace, n) > workspace_bytes) return FNP_ERR_WORKSPACE;
     const int G = fnp_divup(n, kThreads);
 
-    hipLaunchKernelGGL(sweeps_mark_kernel, dim3(G), dim3(kThreads), 0, s, raw, n, sweep_offsets, T, flags, center_radius, w.mask, w.cnt);
+    hipLaunchKernelGGL(sweeps_mark_kernel<kWindow>, dim3(G), dim3(kThreads), 0, s, raw, n, sweep_offsets, T, flags, center_radius, w.mask,
+                       w.cnt);
     FNP_LAUNCH_CHECK();
     int rc = fnp_scan::int32(w.cnt, G, w.base, w.total, w.scan_ws, s);
     if (rc) return rc;
-    hipLaunchKernelGGL(sweeps_offsets_kernel, dim3(fnp_divup(B + 1, kThreads)), dim3(kThreads), 0, s, sweep_offsets, T, scene_sweeps, B, n,
-                       (const unsigned long long *)w.mask, (const int *)w.base, (const int *)w.total, out_offsets);
+    hipLaunchKernelGGL(sweeps_offsets_kernel<kWindow>, dim3(fnp_divup(B + 1, kThreads)), dim3(kThreads), 0, s, sweep_offsets, T, scene_sweeps,
+                       B, n, (const unsigned long long *)w.mask, (const int *)w.base, (const int *)w.total, out_offsets, window_sweeps,
+                       out_window);
     FNP_LAUNCH_CHECK();
-    hipLaunchKernelGGL(sweeps_emit_kernel, dim3(G), dim3(kThreads), 0, s, raw, n, sweep_offsets, T, xform, flags, time_lag,
+    hipLaunchKernelGGL(sweeps_emit_kernel<kWindow>, dim3(G), dim3(kThreads), 0, s, raw, n, sweep_offsets, T, xform, flags, time_lag,
                        (const unsigned long long *)w.mask, (const int *)w.cnt, (const int *)w.base, (const int *)w.total, pad, out_points);
     FNP_LAUNCH_CHECK();
     return FNP_OK;
+}
+
+}  // namespace
+
+extern "C" int fnp_assemble_sweeps(const float *raw, int64_t n_rows, const int *sweep_offsets, int num_sweeps, const int *scene_sweeps,
+                                   int batch_size, const double *xform, const int *flags, const float *time_lag, double center_radius,
+                                   float pad, void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets,
+                                   fnp_stream_t stream) {
+    return assemble<false>(raw, n_rows, sweep_offsets, num_sweeps, scene_sweeps, batch_size, xform, flags, time_lag, center_radius, pad,
+                           workspace, workspace_bytes, out_points, out_offsets, nullptr, nullptr, (hipStream_t)stream);
+}
+
+// fnp_assemble_sweeps with finished-row sweeps (FNP_SWEEP_FINISHED) and a cut window per scene: the same four launches
+extern "C" int fnp_assemble_sweeps_window(const float *raw, int64_t n_rows, const int *sweep_offsets, int num_sweeps,
+                                          const int *scene_sweeps, int batch_size, const double *xform, const int *flags,
+                                          const float *time_lag, double center_radius, float pad, void *workspace,
+                                          int64_t workspace_bytes, float *out_points, int *out_offsets, const int *window_sweeps,
+                                          int *out_window, fnp_stream_t stream) {
+    return assemble<true>(raw, n_rows, sweep_offsets, num_sweeps, scene_sweeps, batch_size, xform, flags, time_lag, center_radius, pad,
+                          workspace, workspace_bytes, out_points, out_offsets, window_sweeps, out_window, (hipStream_t)stream);
 }

@@ -27,6 +27,7 @@ FNP_SHUFFLE_EXPLICIT = 2
 FNP_PREP_MAX_STEPS = 6
 FNP_SWEEP_DROP_EGO = 1
 FNP_SWEEP_TRANSFORM = 2
+FNP_SWEEP_FINISHED = 4
 
 _ERRORS = {-1: "FNP_ERR_ARG", -2: "FNP_ERR_LAUNCH", -3: "FNP_ERR_HIP", -4: "FNP_ERR_WORKSPACE"}
 
@@ -136,6 +137,9 @@ SIGNATURES = {
                                               c_double, c_int, P, c_int64, c_uint64, c_float, P, c_int64, P, P, P]),
     "fnp_assemble_sweeps_workspace_bytes": (c_int64, [c_int64]),
     "fnp_assemble_sweeps": (c_int, [P, c_int64, P, c_int, P, c_int, P, P, P, c_double, c_float, P, c_int64, P, P, P]),
+    "fnp_assemble_sweeps_window": (c_int, [P, c_int64, P, c_int, P, c_int, P, P, P, c_double, c_float, P, c_int64, P, P, P, P, P]),
+    "fnp_rows_in_boxes_workspace_bytes": (c_int64, [c_int64, c_int]),
+    "fnp_rows_in_boxes": (c_int, [P, c_int64, c_int, P, c_int, P, c_int, P, P, c_int, P, P, P, c_int64, P, c_int64, P, P, P, P, P]),
     "fnp_rulebook_subm": (c_int, [P, P, c_int, POINTER(ConvGeom), POINTER(RankGridC), P, P]),
     "fnp_rulebook_strided": (c_int, [P, P, c_int, POINTER(ConvGeom), POINTER(RankGridC), POINTER(RankGridC),
                                      P, P, c_int, P, P, c_int64, P]),

@@ -278,7 +278,7 @@ def prepare_points(points, batch_offsets, batch_size, program, point_cloud_range
     return out
 
 
-def assemble_sweeps(raw, sweep_offsets, scene_sweeps, xform, flags, time_lag, batch_size, center_radius=1.0, out=None):
+def assemble_sweeps(raw, sweep_offsets, scene_sweeps, xform, flags, time_lag, batch_size, center_radius=1.0, out=None, window=None):
     """NuScenesDataset.get_lidar_with_sweeps of a batch on the device, in front of prepare_points (fnp_assemble_sweeps).
 
     The six arrays of datasets.nuscenes_sweeps.pack_sweeps, as device tensors, for batch_size scenes holding T sweeps in all (a
@@ -289,6 +289,12 @@ def assemble_sweeps(raw, sweep_offsets, scene_sweeps, xform, flags, time_lag, ba
     |y| < center_radius), bit 1 applies xform (a key frame carries neither, a sweep without a matrix not bit 1);
     time_lag (T,) f32: the fifth output column.
     out: a dict returned by an earlier call with the same R and B, whose buffers are reused (a captured graph's static outputs).
+    window: None, or the seventh array of pack_sweeps(..., lead=, tail=): (B,2) int32 device, per scene the sweep range
+    [first, end) whose rows gt_sampling's cut may drop (fnp_assemble_sweeps_window).  Only with a window may a sweep carry bit 2
+    (FNP_SWEEP_FINISHED): its rows are finished (x, y, z, intensity, lag) rows and leave as they came, column 4 included.  The
+    returned dict then also holds window (B,2) int32 and its columns cut_from and cut_to, (B,) int32: scene b's kept rows in front
+    of the window's first and end row, relative to batch_offsets[b] — elements 2 and 3 of prepare_points' 4-tuple cut and of
+    rows_in_boxes' cut.
 
     Returns dict(points (R,5) f32: each scene's kept rows in raw order, scene after scene, then PREP_PAD rows; batch_offsets
     (B+1,) int32; n (1,) int32: the kept count; batch_size; workspace) — points and batch_offsets are what prepare_points,
@@ -306,6 +312,9 @@ def assemble_sweeps(raw, sweep_offsets, scene_sweeps, xform, flags, time_lag, ba
     assert time_lag.dtype == torch.float32 and time_lag.numel() == T and time_lag.is_contiguous()
     n = raw.shape[0]
     dev = raw.device
+    if window is not None:
+        _l.require_device(window)
+        assert window.dtype == torch.int32 and tuple(window.shape) == (batch_size, 2) and window.is_contiguous()
     ws_bytes = int(L.fnp_assemble_sweeps_workspace_bytes(n))
     _l.check(min(ws_bytes, 0), "fnp_assemble_sweeps_workspace_bytes")
     if out is None:
@@ -313,14 +322,87 @@ def assemble_sweeps(raw, sweep_offsets, scene_sweeps, xform, flags, time_lag, ba
                    workspace=torch.empty((ws_bytes,), dtype=torch.uint8, device=dev))
         off = torch.empty((batch_size + 1,), dtype=torch.int32, device=dev)
         out.update(batch_offsets=off, n=off[batch_size:], batch_size=batch_size)
+        if window is not None:
+            out["window"] = torch.empty((batch_size, 2), dtype=torch.int32, device=dev)
+            out["cut_from"] = torch.empty((batch_size,), dtype=torch.int32, device=dev)
+            out["cut_to"] = torch.empty((batch_size,), dtype=torch.int32, device=dev)
     else:
         assert out["points"].shape == (n, 5) and out["batch_offsets"].numel() == batch_size + 1 and out["workspace"].numel() >= ws_bytes
-    rc = L.fnp_assemble_sweeps(_l.ptr(raw) if n else None, n, _l.ptr(sweep_offsets), T, _l.ptr(scene_sweeps), batch_size,
-                               _l.ptr(xform) if T else None, _l.ptr(flags) if T else None, _l.ptr(time_lag) if T else None,
-                               float(center_radius), PREP_PAD, _l.ptr(out["workspace"]), out["workspace"].numel(),
-                               _l.ptr(out["points"]) if n else None, _l.ptr(out["batch_offsets"]), _l.stream())
-    _l.check(rc, "fnp_assemble_sweeps")
+        assert window is None or tuple(out["window"].shape) == (batch_size, 2)
+    args = (_l.ptr(raw) if n else None, n, _l.ptr(sweep_offsets), T, _l.ptr(scene_sweeps), batch_size,
+            _l.ptr(xform) if T else None, _l.ptr(flags) if T else None, _l.ptr(time_lag) if T else None,
+            float(center_radius), PREP_PAD, _l.ptr(out["workspace"]), out["workspace"].numel(),
+            _l.ptr(out["points"]) if n else None, _l.ptr(out["batch_offsets"]))
+    if window is None:
+        _l.check(L.fnp_assemble_sweeps(*args, _l.stream()), "fnp_assemble_sweeps")
+        return out
+    _l.check(L.fnp_assemble_sweeps_window(*args, _l.ptr(window), _l.ptr(out["window"]), _l.stream()), "fnp_assemble_sweeps_window")
+    out["cut_from"].copy_(out["window"][:, 0])   # (the entry writes (B, 2); the cut takes two contiguous (B,) arrays)
+    out["cut_to"].copy_(out["window"][:, 1])
     return out
+
+
+def rows_in_boxes(points, batch_offsets, batch_size, records, box_offsets, cut=None, capacity=4096, out=None):
+    """The rows of a batch inside boxes, compact, on the device (fnp_rows_in_boxes): augmentor.pseudo_loader's
+    points_in_boxes_compact for scenes that exist only on the card.
+
+    points (N,5) f32 device and batch_offsets (B+1,) int32 device: the output of assemble_sweeps.  records (T,8) f32 device:
+    augmentor.database_sampler.cut_records of the boxes, scene after scene; box_offsets (B+1,) int32 device: scene b's boxes.
+    cut: None, or the pending cut (records (M,8) f32, offsets (B+1,) int32, cut_from (B,) int32, cut_to (B,) int32), device
+    tensors — the 4-tuple of prepare_points: rows it will drop are left out.
+    capacity: the rows that `indices` and `rows` can hold.  out: a dict returned by an earlier call with the same shapes.
+
+    Returns dict(counts (T,) int32: rows inside each box, always complete; total (1,) int32; indices (capacity,) int32: the
+    scene-relative row index and rows (capacity,5) f32: the raw row of the first `capacity` rows inside, box after box, in row
+    order inside a box; capacity; workspace).  The membership test is the host's (faces inclusive), bit for bit.  No host sync,
+    fixed shapes: capturable.  rows_in_boxes_exact reads the result and repeats the call when total > capacity."""
+    L = _l.load()
+    _l.require_device(points, batch_offsets, records, box_offsets)
+    assert points.dtype == torch.float32 and points.dim() == 2 and points.shape[1] == 5 and points.is_contiguous()
+    assert points.data_ptr() % 16 == 0, "points: a 16-byte aligned buffer"
+    assert batch_offsets.dtype == torch.int32 and batch_offsets.numel() == batch_size + 1 and batch_offsets.is_contiguous()
+    assert records.dtype == torch.float32 and records.dim() == 2 and records.shape[1] == 8 and records.is_contiguous()
+    assert box_offsets.dtype == torch.int32 and box_offsets.numel() == batch_size + 1 and box_offsets.is_contiguous()
+    n, T, capacity, dev = points.shape[0], records.shape[0], int(capacity), points.device
+    M = 0
+    cut_args = (None, 0, None, None, None)
+    if cut is not None:
+        c_rec, c_off, c_from, c_to = cut
+        _l.require_device(c_rec, c_off, c_from, c_to)
+        assert c_rec.dtype == torch.float32 and c_rec.dim() == 2 and c_rec.shape[1] == 8 and c_rec.is_contiguous()
+        assert c_off.dtype == torch.int32 and c_off.numel() == batch_size + 1 and c_off.is_contiguous()
+        for t in (c_from, c_to):
+            assert t.dtype == torch.int32 and t.numel() == batch_size and t.is_contiguous()
+        M = int(c_rec.shape[0])
+        if M:
+            cut_args = (_l.ptr(c_rec), M, _l.ptr(c_off), _l.ptr(c_from), _l.ptr(c_to))
+    ws_bytes = int(L.fnp_rows_in_boxes_workspace_bytes(n, T))
+    _l.check(min(ws_bytes, 0), "fnp_rows_in_boxes_workspace_bytes")
+    if out is None:
+        out = dict(counts=torch.empty((T,), dtype=torch.int32, device=dev), total=torch.empty((1,), dtype=torch.int32, device=dev),
+                   indices=torch.empty((capacity,), dtype=torch.int32, device=dev),
+                   rows=torch.empty((capacity, 5), dtype=torch.float32, device=dev), capacity=capacity,
+                   workspace=torch.empty((ws_bytes,), dtype=torch.uint8, device=dev))
+    else:
+        assert out["counts"].numel() == T and out["capacity"] == capacity and out["workspace"].numel() >= ws_bytes
+    rc = L.fnp_rows_in_boxes(_l.ptr(points) if n else None, n, 5, _l.ptr(batch_offsets), batch_size, _l.ptr(records) if T else None, T,
+                             _l.ptr(box_offsets), *cut_args, capacity, _l.ptr(out["workspace"]), out["workspace"].numel(),
+                             _l.ptr(out["counts"]) if T else None, _l.ptr(out["total"]), _l.ptr(out["indices"]) if capacity else None,
+                             _l.ptr(out["rows"]) if capacity else None, _l.stream())
+    _l.check(rc, "fnp_rows_in_boxes")
+    return out
+
+
+def rows_in_boxes_exact(points, batch_offsets, batch_size, records, box_offsets, cut=None, capacity=4096):
+    """rows_in_boxes read back once: (counts (T,) int64, indices (K,) int32, rows (K,5) f32) as numpy arrays, K = counts.sum().
+    Synchronises (one device-to-host copy of counts and total, one of the rows); when total > capacity the call is repeated with
+    the exact size, the protocol of the host wrapper."""
+    res = rows_in_boxes(points, batch_offsets, batch_size, records, box_offsets, cut=cut, capacity=capacity)
+    head = torch.cat([res["total"], res["counts"]]).cpu().numpy()
+    total = int(head[0])
+    if total > res["capacity"]:
+        res = rows_in_boxes(points, batch_offsets, batch_size, records, box_offsets, cut=cut, capacity=total)
+    return head[1:].astype("int64"), res["indices"][:total].cpu().numpy(), res["rows"][:total].cpu().numpy()
 
 
 def voxelize(points, batch_offsets, batch_size, cfg, grid=None, want_voxels=False, workspace=None):

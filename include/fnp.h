@@ -299,7 +299,7 @@ int fnp_prepare_points_cut_window(const float *points, int64_t n_points, int num
  * Multi-sweep assembly in front of fnp_prepare_points — replaces, on the device, NuScenesDataset.get_lidar_with_sweeps and
  * get_sweep (pcdet/datasets/nuscenes/nuscenes_dataset.py:88-121), which the reference runs in numpy inside DataLoader workers.
  * ------------------------------------------------------------------------------------------ */
-enum { FNP_SWEEP_DROP_EGO = 1, FNP_SWEEP_TRANSFORM = 2 };
+enum { FNP_SWEEP_DROP_EGO = 1, FNP_SWEEP_TRANSFORM = 2, FNP_SWEEP_FINISHED = 4 /* fnp_assemble_sweeps_window only */ };
 
 int64_t fnp_assemble_sweeps_workspace_bytes(int64_t n_rows);
 
@@ -321,6 +321,43 @@ int fnp_assemble_sweeps(const float *raw, int64_t n_rows, const int *sweep_offse
                         int batch_size, const double *xform, const int *flags, const float *time_lag, double center_radius,
                         float pad, void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets,
                         fnp_stream_t stream);
+
+/* fnp_assemble_sweeps with finished-row sweeps and a cut window per scene (same workspace, same four launches).
+ * FNP_SWEEP_FINISHED: the sweep's rows are finished (x, y, z, intensity, lag) rows — gt-sampled database objects in front of
+ *   the scene, pasted objects behind it: all five columns leave as they came, bit for bit; time_lag[t] is not read, and
+ *   FNP_SWEEP_DROP_EGO / FNP_SWEEP_TRANSFORM on the same sweep are ignored (the caller should not set them).
+ * window_sweeps (B, 2) int32 device: the rows of scene b that gt_sampling's cut may drop are those of the sweeps
+ *   [window_sweeps[b][0], window_sweeps[b][1]), sweep indices into the T sweeps, clamped into the scene's own range.
+ * out_window (B, 2) int32 device: {kept rows of scene b in front of the window's first raw row, kept rows of scene b in front
+ *   of the window's end row}, both relative to out_offsets[b]: the cut_from / cut_to arrays of fnp_prepare_points_cut_window
+ *   and fnp_rows_in_boxes as out_window[2 * b] and out_window[2 * b + 1].
+ * No atomics, no host synchronisation: capturable. */
+int fnp_assemble_sweeps_window(const float *raw, int64_t n_rows, const int *sweep_offsets, int num_sweeps, const int *scene_sweeps,
+                               int batch_size, const double *xform, const int *flags, const float *time_lag, double center_radius,
+                               float pad, void *workspace, int64_t workspace_bytes, float *out_points, int *out_offsets,
+                               const int *window_sweeps, int *out_window, fnp_stream_t stream);
+
+/* The rows inside boxes, compact, for a batch on the device: fnp_host_points_in_boxes_compact for the scenes that
+ * fnp_assemble_sweeps leaves on the card (unknowns_copy_paste feeds its queue from them).  All arrays on the device:
+ * points (N, 5) f32, 16-byte aligned, and batch_offsets (B+1,) int32: the assembly's output (rows behind batch_offsets[B] are
+ *   ignored); num_features must be 5;
+ * box_records (T, 8) f32 in the layout of fnp_host_cut_records {cx, cy, cz, dx, dy, dz, cos(-h), sin(-h)} and box_offsets (B+1,)
+ *   int32: scene b's boxes are [box_offsets[b], box_offsets[b+1]) and are tested against that scene's rows only, with the
+ *   INCLUSIVE test of fnp_host_points_in_boxes_frame (same expressions, f32, uncontracted);
+ * the pending cut (num_cut_records == 0: none): cut_records (M, 8), cut_offsets (B+1,), cut_from (B,), cut_to (B,) as
+ *   fnp_prepare_points_cut_window takes them; a row with cut_from[b] <= i - batch_offsets[b] < cut_to[b] inside one of the
+ *   scene's cut records is left out.
+ * Outputs: counts (T,) int32, always complete; total (1,) int32, their sum; indices (capacity,) int32 and rows (capacity, 5) f32:
+ *   the first `capacity` rows inside, box after box, in row order inside a box: the scene-relative row index and the RAW row
+ *   (the host form returns box-frame rows; the caller makes them).  When total > capacity call again with that size.
+ * Deterministic, no atomics, no host synchronisation, fixed launch sequence for fixed shapes: capturable.
+ * num_boxes * ceil(N / 256) < 2^31. */
+int64_t fnp_rows_in_boxes_workspace_bytes(int64_t n_points, int num_boxes);
+int fnp_rows_in_boxes(const float *points, int64_t n_points, int num_features, const int *batch_offsets, int batch_size,
+                      const float *box_records, int num_boxes, const int *box_offsets, const float *cut_records,
+                      int num_cut_records, const int *cut_offsets, const int *cut_from, const int *cut_to, int64_t capacity,
+                      void *workspace, int64_t workspace_bytes, int *counts, int *total, int *indices, float *rows,
+                      fnp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
  * Rulebooks — replace spconv's indice-pair generation for SubMConv3d / SparseConv3d
