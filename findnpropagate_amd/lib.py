@@ -196,6 +196,13 @@ SIGNATURES = {
     "fnp_sparse_to_dense": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int64, P]),
     "fnp_sparse_to_dense_fill": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, c_int64, P]),
     "fnp_sparse_to_dense_backward": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int64, P]),
+    "fnp_heatmap_box_params": (c_int, [P, c_int, c_int, c_int, c_int, c_float, c_float, c_int, c_float, c_float, c_double, c_int,
+                                       c_uint64, c_double, P, P]),
+    "fnp_heatmap_draw_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "fnp_heatmap_draw": (c_int, [P, c_int, c_int, c_int, c_int, c_int, P, c_int64, P, P, P]),
+    "fnp_heatmap_loss_workspace_bytes": (c_int64, [c_int64]),
+    "fnp_heatmap_loss_forward": (c_int, [P, c_int, P, c_int64, P, P, c_int64, P, P]),
+    "fnp_heatmap_loss_backward": (c_int, [P, c_int, P, c_int64, P, P, P, P]),
 }
 
 

@@ -1,3 +1,3 @@
-from . import model_nms_utils
+from . import centernet_utils, model_nms_utils, transfusion_utils
 
-__all__ = ["model_nms_utils"]
+__all__ = ["centernet_utils", "model_nms_utils", "transfusion_utils"]

@@ -814,6 +814,39 @@ int fnp_boxseeker(const float *points, const int *scene_offsets, int num_scenes,
 int fnp_seeker_pack_records(const float *frustums, const int *out_valid, const float *out_box, int num_frustums,
                             const float *tags, int num_scenes, int rows_per_scene, float *records, fnp_stream_t stream);
 
+/* Dense heatmap targets and heatmap loss of TransFusionHead (transfusion_head.py:446-470, :492-498; additive, ABI 14).
+ * All three steps take a stream, allocate nothing and do not synchronise.
+ *
+ * fnp_heatmap_box_params: gt_boxes (B, M, ncol) f32, x y z dx dy dz ... label (last column, 1-based, 0 = padding) ->
+ * out_params (B, M, 4) int32 {class (0-based), cx, cy, r}, 16-byte aligned.  class = -1 marks a skipped box: dx or dy <= 0, a
+ * non-finite x, y, dx or dy, or a label outside 1..num_classes (the reference raises on a label above num_classes and wraps
+ * on one below 1; both are out of contract here).  voxel_*, range_* are voxel_size[0:2] and point_cloud_range[0:2] rounded to
+ * f32; overlap = GAUSSIAN_OVERLAP, min_radius = MIN_RADIUS; unknown_mask has bit (label - 1) set for every 1-based label in
+ * unknown_labels (0 when use_pseudo is off), whose radius becomes int(r * unknown_mult) in f64.  The arithmetic is the
+ * reference's as torch runs it on the CPU, bit for bit.  A radius is clamped to 2^20 and a centre to +-2^30 cells.
+ *
+ * fnp_heatmap_draw: params as above -> heatmap (B, C, H, W) f32 (H along y, W along x), every element written exactly once
+ * (no clear pass, no atomics, independent of box order), and num_pos (1) int32 = the number of elements equal to 1.
+ * workspace: fnp_heatmap_draw_workspace_bytes(B, C, H, W), 4-byte aligned.
+ *
+ * fnp_heatmap_loss_forward: loss (1) f32 = sum(GaussianFocalLoss(alpha 2, gamma 4)(clip_sigmoid(logits), target)) /
+ * max(*num_pos, 1).  logits: n values of `dtype` (FNP_F32, FNP_F16, FNP_BF16), upcast exactly and NOT modified (the
+ * reference's sigmoid_ overwrites them); target n f32; arithmetic in f32, the sum in f64 in a fixed order: bit-identical from
+ * run to run.  workspace: fnp_heatmap_loss_workspace_bytes(n), 8-byte aligned.
+ * fnp_heatmap_loss_backward: grad_logits (n, `dtype`) = dT/dlogit * (*grad_out / max(*num_pos, 1)), recomputed from logits
+ * and target; exactly 0 where the sigmoid lies outside the clamp. */
+int fnp_heatmap_box_params(const float *gt_boxes, int batch_size, int max_boxes, int ncol, int num_classes, float voxel_x,
+                           float voxel_y, int stride, float range_x, float range_y, double overlap, int min_radius,
+                           uint64_t unknown_mask, double unknown_mult, int *out_params, fnp_stream_t stream);
+int64_t fnp_heatmap_draw_workspace_bytes(int batch_size, int num_classes, int height, int width);
+int fnp_heatmap_draw(const int *params, int batch_size, int max_boxes, int num_classes, int height, int width,
+                     void *workspace, int64_t workspace_bytes, float *heatmap, int *num_pos, fnp_stream_t stream);
+int64_t fnp_heatmap_loss_workspace_bytes(int64_t n);
+int fnp_heatmap_loss_forward(const void *logits, int dtype, const float *target, int64_t n, const int *num_pos,
+                             void *workspace, int64_t workspace_bytes, float *loss, fnp_stream_t stream);
+int fnp_heatmap_loss_backward(const void *logits, int dtype, const float *target, int64_t n, const int *num_pos,
+                              const float *grad_out, void *grad_logits, fnp_stream_t stream);
+
 /* Capacity overflow: data-dependent counts (n_voxels, n_out) always hold the TRUE count; every
  * kernel clamps to the capacity it was given, so a count larger than its capacity means rows
  * were dropped and the caller must re-run with larger buffers. */
