@@ -355,9 +355,6 @@ class VoxelResBackBone8x(_BackboneBase):
             yield pipe.result()
 
 
-X3_FUSED = os.environ.get("FNP_X3_FUSED", "1") != "0"   # bf16x3: the main product's epilogue adds the cross terms and writes the split
-X3_FAST = os.environ.get("FNP_X3_FAST", "1") != "0"   # bf16x3: cross terms on the bf16-out fast kernels (0: three f32-out gather launches per layer)
-
 # the fused engine's index chain on a side stream (FusedResBackbone._run_once): None = while a hipGraph is being captured (the
 # replayed graph runs the two branches side by side, the ~4.5 us between its nodes overlap: +4 to +10 % from 1 to 64 scenes),
 # not for stream launches (measured neutral within a box's +-1.5 %: back-to-back launches have no such gaps to hide);
@@ -386,18 +383,19 @@ class _PointsGraph:
         # HOST COUNTS (round 6, every capture that is not a probe): the counts launch stores the counts into pinned host memory itself
         # and its sequence number behind them (fnp_gather_counts_host); counts() polls for that number.  No event, no copy — and no
         # cut: the convolutions are ONE graph, the last SubM stage follows the strided layer in front of it without the ~25 us a
-        # one-scene forward spent between two graph launches (end of graph, counts copy, event, start of graph).  FNP_HOST_COUNTS=0:
-        # the two-graph form with the copy between them.
-        self.host_counts = (not probe) and os.environ.get("FNP_HOST_COUNTS", "1") != "0"
-        self.counts_seq, self._replays = None, 0
+        # one-scene forward spent between two graph launches (end of graph, counts copy, event, start of graph).
+        self.probe, self.deferred = bool(probe), []
+        self.host_counts = not self.probe
         self.split_index, self.graph_i, self._index_cut = bool(split_index), None, False
-        self.probe, self.deferred, self.graph_b = bool(probe), [], None
-        self.counts_dev, self.counts_pin = None, None
+        self.counts_dev = None
         if self.host_counts:    # (allocated and zeroed HERE: a fill issued during the capture would be a node of the graph)
             self.counts_pin = torch.zeros((32,), dtype=torch.int32, pin_memory=True)
             self._pin_np = self.counts_pin.numpy()
-            self.counts_seq = torch.zeros((1,), dtype=torch.int32, device=device)
-        self.counts_event, self.done_event = torch.cuda.Event(), torch.cuda.Event()
+            self.counts_seq, self._replays = torch.zeros((1,), dtype=torch.int32, device=device), 0
+        else:
+            self.counts_pin = torch.empty((16,), dtype=torch.int32, pin_memory=True)
+            self.graph_b, self.counts_event = torch.cuda.CUDAGraph(), torch.cuda.Event()
+        self.done_event = torch.cuda.Event()
         self._replayed = False
         self.engine, self.capacity, self.batch_size = engine, capacity, batch_size
         self.pts = torch.full((capacity, n_feat), self.FAR, dtype=torch.float32, device=device)
@@ -425,7 +423,6 @@ class _PointsGraph:
         gc.collect()
         gc.disable()
         try:
-            self.graph_b = torch.cuda.CUDAGraph()
             if self.split_index:
                 self.graph_i = torch.cuda.CUDAGraph()
                 self._ctx = torch.cuda.graph(self.graph_i)
@@ -433,12 +430,10 @@ class _PointsGraph:
                 self._ctx = torch.cuda.graph(self.graph)
             self._ctx.__enter__()
             try:
-                self.vox, self.res = self._body(voxel_cfg)   # (the engine calls counts_ready() where the first graph ends)
+                self.vox, self.res = self._body(voxel_cfg, capture=True)   # (the engine calls counts_ready() where the counts are final)
             finally:
                 self._ctx.__exit__(None, None, None)
             assert self.counts_dev is not None and (self.deferred or not self.probe), "the engine did not reach its cut"
-            if self.host_counts:
-                self.graph_b = None     # (never begun: the capture was not cut)
             assert self._index_cut or not self.split_index, "the engine did not cut behind its index chain"
         finally:
             if gc_was_on:
@@ -468,13 +463,9 @@ class _PointsGraph:
         self._ctx = torch.cuda.graph(self.graph, pool=self.graph_i.pool())
         self._ctx.__enter__()
 
-    def counts_host(self):
-        """(pinned tensor, device sequence word) the engine's counts launch writes to, or None (two-graph form: replay() copies)"""
-        return (self.counts_pin, self.counts_seq) if self.host_counts else None
-
     def counts_ready(self, counts_dev):
-        """called by the engine where the counts are final (every forked stream rejoined): ends the first graph's capture and
-        begins the second's on the same capture stream and memory pool (host counts: nothing to cut)"""
+        """called by the engine where the counts are final (every forked stream rejoined).  A probe: ends the first graph's capture
+        and begins the second's on the same capture stream and memory pool (host counts: nothing to cut)"""
         self.counts_dev = counts_dev
         if self.host_counts:
             return
@@ -508,14 +499,9 @@ class _PointsGraph:
         self.graph.replay()
         if self.host_counts:
             self._replays += 1
-            self.done_event.record()
-            self.engine._last_done = self.done_event
-            return
-        if self.counts_pin is None:
-            self.counts_pin = torch.empty((16,), dtype=torch.int32, pin_memory=True)
-        self.counts_pin[:self.counts_dev.numel()].copy_(self.counts_dev, non_blocking=True)
-        self.counts_event.record()
-        if self.probe:
+        else:
+            self.counts_pin[:self.counts_dev.numel()].copy_(self.counts_dev, non_blocking=True)
+            self.counts_event.record()
             for tag, launch in self.deferred:
                 if profile is None:
                     launch()
@@ -525,7 +511,7 @@ class _PointsGraph:
                     launch()
                     e1.record()
                     profile.append((tag, e0, e1))
-        self.graph_b.replay()
+            self.graph_b.replay()
         self.done_event.record()
         self.engine._last_done = self.done_event     # an eager forward issued next, on any stream, waits for this replay
 
@@ -552,7 +538,7 @@ class _PointsGraph:
         self.counts_event.synchronize()
         return self.counts_pin[:self.counts_dev.numel()].tolist()
 
-    def _body(self, voxel_cfg):
+    def _body(self, voxel_cfg, capture=False):
         e = self.engine
         e._ensure_clean()
         e._dirty = True
@@ -560,7 +546,7 @@ class _PointsGraph:
         vox = S.voxelize(self.pts, self.off, self.batch_size, voxel_cfg, grid=grids[0], workspace=e._vox_ws)
         e._vox_ws = vox['workspace']
         res = e._run_once(vox['mean'], vox['coords'], vox['n'], self.batch_size, grids[0], sync=False, n_cells=vox['n_cells'],
-                          probe=self if self.graph_b is not None else None)
+                          probe=self if capture else None)
         return vox, res
 
 
@@ -589,7 +575,7 @@ class PointsPipeline:
         for e in self.engines:
             # two frames in flight already put one frame's index kernels under another's convolutions; a second branch per
             # graph on top of that oversubscribes the hardware queues
-            e.two_streams = self.depth == 1 or os.environ.get("FNP_PIPE_TWO", "0") == "1"
+            e.two_streams = self.depth == 1
 
         # Which streams: ones that were SEEN to run beside each other and beside the caller's (concurrent_streams: the card's four
         # hardware queues are shared out in the order streams are first used, and two streams of one queue run one after the other).
@@ -598,8 +584,7 @@ class PointsPipeline:
         # streams than queues (three slots + the convolution stream + the caller's) the CONVOLUTION stream is the one kept apart and the
         # slots double up: their index chains run one after the other anyway.  FNP_TESTED_STREAMS=0: torch's next pool streams;
         # `streams` hands in the caller's own.
-        env = {"0": False, "1": True}.get(os.environ.get("FNP_PIPE_SERIAL", ""))
-        self.serial_convs = self.depth > 1 and (bool(serial_convs) if serial_convs is not None else env if env is not None else self.batch_size >= 8)
+        self.serial_convs = self.depth > 1 and (bool(serial_convs) if serial_convs is not None else self.batch_size >= 8)
         if streams is not None:     # (the caller's own: depth slot streams, then the convolution stream of the serial form)
             picked = list(streams)
             assert len(picked) == self.depth + (1 if self.serial_convs else 0)
@@ -623,7 +608,7 @@ class PointsPipeline:
         # waves per CU) running under ANOTHER batch's convolutions — so each slot's capture is cut behind its index chain
         # (_PointsGraph split_index): the index graph goes to the slot's stream, the convolution graphs of ALL slots to one
         # stream in submission order.  Default: on for batches of >= 8 scenes (convolutions that fill the chip); a one-scene
-        # stream, whose convolutions leave most CUs idle, keeps the free-for-all.  FNP_PIPE_SERIAL=0 / 1 forces.
+        # stream, whose convolutions leave most CUs idle, keeps the free-for-all.  `serial_convs` forces either.
         # Measured at 128 scenes (one box, bench.py): one batch at a time 12.50 k scenes/s; serial, two / three in flight 12.79-13.07 /
         # 12.84-13.04 k with the dominant kernel at 0.76-0.78 ms; free-for-all 13.10-13.12 / 13.42 k with it at 1.37 ms.  A kernel
         # trace of the serial form (tools/pipe_trace.sh) shows a gapless convolution chain (0.24 ms of gaps per step) whose early
@@ -665,7 +650,7 @@ class PointsPipeline:
         st.wait_stream(torch.cuda.current_stream(self.device))   # the caller produced `points` on its own stream
         with torch.cuda.stream(st):
             g.stage(points, batch_offsets)
-            # (copies the counts to pinned memory between its two convolution graphs; done_event at the end)
+            # (the counts launch inside the graph stores the counts into the slot's pinned memory; done_event at the end)
             g.replay(self.profile if self.probe else None, conv_stream=self.conv_stream)
         points.record_stream(st)
         batch_offsets.record_stream(st)
@@ -677,32 +662,20 @@ class PointsPipeline:
         g, e = self.slots[d], self.engines[d]
         counts = g.counts()
         ev = g.done_event
-        overflow = e._ell_overflow(counts, g.res['ell_used'], g.res['caps'][0])
-        e._check_aborts(counts.pop())
-        caps = g.res['caps']
-        overflow = overflow or any(counts[l] > caps[l] for l in range(1, 5))
+        overflow = e._digest_counts(counts, g.res['ell_used'], g.res['caps'])
         torch.cuda.current_stream(self.device).wait_event(ev)   # the caller's stream reads the slot's buffers next
         if overflow:
-            # a capacity was too small for this frame: the engine's own loop grows it and recaptures (synchronously; rare)
+            # a capacity was too small for this frame (and has been grown): the engine's own loop recaptures (synchronously; rare)
             ev.synchronize()
             for pd, _, _ in self.pending:
                 self.slots[pd].done_event.synchronize()
-            for l in range(1, 5):
-                if counts[l] > caps[l]:
-                    e.cap_factor[l - 1] = max(e.cap_factor[l - 1] * 2.0, counts[l] * 1.25 / caps[0])
             torch.cuda.synchronize(self.device)
             for gr in e._get_grids(self.batch_size, self.device):   # rows beyond a capacity were never emitted: the sparse clear missed their cells
                 gr.zero_()
             e._dirty = False
             self.slots[d] = None
             return e.run_points_graphed(points, batch_offsets, self.batch_size, self.cfg, self.capacity)
-        stage, shapes = g.res['stages'], g.res['shapes']
-        tensors = [spconv.SparseConvTensor(x[:counts[l]], idx[:counts[l]], shapes[l], self.batch_size, n_dev=nd)
-                   for l, (x, idx, nd, _) in enumerate(stage)]
-        n1 = counts[0]
-        return {'x_conv1': tensors[0], 'x_conv2': tensors[1], 'x_conv3': tensors[2], 'x_conv4': tensors[3],
-                'out': tensors[4], 'counts': counts, 'voxel_coords': g.vox['coords'][:n1],
-                'voxel_num_points': g.vox['num_points'][:n1], 'voxel_features': g.vox['mean'][:n1]}
+        return e._results(g.res['stages'], counts, g.res['shapes'], self.batch_size, vox=g.vox)
 
     def map(self, frames):
         """generator over an iterable of (points, batch_offsets): results in order, `depth` frames in flight"""
@@ -761,13 +734,6 @@ class FusedResBackbone:
         self.rulebook_log = None
         # hand-over time-outs of the tiled 32-channel kernel (csrc/spconv_tile.hip g_tile_aborts): the library-wide counter
         # is copied behind every forward into a device word that travels with the per-stage counts of the one host sync
-
-    def _aborts_word(self, device):
-        """enqueue a copy of the library's time-out counter; returns the (1,) int32 device tensor it lands in"""
-        from .. import lib as _l
-        t = torch.empty((1,), dtype=torch.int32, device=device)
-        _l.check(_l.load().fnp_spconv_tiled_aborts_copy(_l.ptr(t), _l.stream()), "fnp_spconv_tiled_aborts_copy")
-        return t
 
     def _counts_word(self, stage, ell_used, device, host=None):
         """enqueue ONE launch that collects what the host reads in a forward's one synchronisation — the five stage counts, the
@@ -845,6 +811,32 @@ class FusedResBackbone:
                 over = True
         return over
 
+    def _digest_counts(self, counts, ell_used, caps):
+        """what the host does with a forward's counts as read back (_counts_word: five stage counts, the time-out word, the pool
+        and escape counters): grows the pools and runs the tile gate, raises on a tile time-out, grows the capacity factor of
+        every stage whose count exceeds its capacity.  Leaves the five stage counts in `counts`; True: the forward must be rerun
+        with the grown buffers (what has to be synchronised and wiped before that is the caller's)."""
+        rerun = self._ell_overflow(counts, ell_used, caps[0])
+        self._check_aborts(counts.pop())
+        for l in range(1, 5):
+            if counts[l] > caps[l]:
+                self.cap_factor[l - 1] = max(self.cap_factor[l - 1] * 2.0, counts[l] * 1.25 / caps[0])
+                rerun = True
+        return rerun
+
+    @staticmethod
+    def _results(stage, counts, shapes, batch_size, vox=None):
+        """the dict a forward returns: the five stages' (features, indices, n_dev, grid) cut to their counts; vox (the voxeliser's
+        outputs): its coordinates, point counts and means cut to the stage-1 count as well"""
+        tensors = [spconv.SparseConvTensor(x[:counts[l]], idx[:counts[l]], shapes[l], batch_size, n_dev=nd)
+                   for l, (x, idx, nd, _) in enumerate(stage)]
+        res = {'x_conv1': tensors[0], 'x_conv2': tensors[1], 'x_conv3': tensors[2], 'x_conv4': tensors[3],
+               'out': tensors[4], 'counts': counts}
+        if vox is not None:
+            n1 = counts[0]
+            res.update({'voxel_coords': vox['coords'][:n1], 'voxel_num_points': vox['num_points'][:n1], 'voxel_features': vox['mean'][:n1]})
+        return res
+
     # ---- weights --------------------------------------------------------------------------
     def _fold(self, conv, bn, dtype):
         """packed weight + BatchNorm(eval) as per-channel scale / shift.  The fold runs on the HOST in IEEE f32 —
@@ -897,6 +889,7 @@ class FusedResBackbone:
         w32, scale, shift = self._fold(conv, bn, torch.float32)
         w32 = w32.as_subclass(torch.Tensor) if isinstance(w32, S.PermutedWeight) else w32
         wf = S.pack_weight(conv.weight, torch.float32).float() * scale.view(1, -1, 1)      # plain (K, Cout, Cin) layout
+        assert (int(wf.shape[2]), int(wf.shape[1])) in S.SPLIT_SHAPES, "bf16x3: no split kernel (conv_forward_split) for this layer's channels"
         hi = wf.to(torch.bfloat16)
         lo = (wf - hi.float()).to(torch.bfloat16)
         return (hi.contiguous(), lo.contiguous(), torch.ones_like(scale)), None, shift
@@ -905,35 +898,23 @@ class FusedResBackbone:
         hi, lo = S.split_bf16(y, n)
         return (hi, lo, y)
 
-    def _conv_x3(self, x, prm, rb, n, residual, out, ranked=False, want_f32=True):
+    def _conv_x3(self, x, prm, rb, n, residual, ranked=False, want_f32=True):
         """one convolution of the bf16x3 engine (see __init__): x = (hi, lo, f32 rows); returns the same triple of the output
         (want_f32=False: the f32 rows are None — the first convolution of a residual block, of which only the split is read)"""
         (whi, wlo, ones), _, shift = prm
         res = None if residual is None else residual[2]
         C = int(whi.shape[1])
-        fast = X3_FAST and ranked and (C in getattr(rb, "_tile_rb", {}) or (C == 128 and getattr(rb, "_sorted", None) is not None))
-        if X3_FAST and X3_FUSED and (fast or (int(whi.shape[2]), C) in S.SPLIT_SHAPES):
-            # the two cross terms are 2^-8 of the result: bf16 precision is enough for them, so they run with bf16 outputs (on the
-            # bf16 engine's tile-rulebook / class-sorted kernels where the stage has them) chained through a bf16 residual; only the
-            # main product keeps f32, and ITS epilogue adds them, applies the ReLU and writes the f32 rows with their (hi, lo) split
-            # (conv_forward_split; FNP_X3_FUSED=0: f32-out gather kernel + a split pass)
-            kw = dict(ranked=True) if fast else dict(tile=False)
-            t = S.conv_forward(x[1], whi, rb, n, **kw)
-            t = S.conv_forward(x[0], wlo, rb, n, residual=t, out=t, **kw)
-            y, hi, lo = S.conv_forward_split(x[0], whi, rb, n, scale=ones, shift=shift, residual=res, addend=t, relu=True, ranked=ranked,
-                                             tile=None if fast else False, want_f32=want_f32)
-            return (hi, lo, y)
-        if fast:
-            t = S.conv_forward(x[1], whi, rb, n, ranked=True)
-            t = S.conv_forward(x[0], wlo, rb, n, residual=t, ranked=True, out=t)
-            y = S.conv_forward(x[0], whi, rb, n, out_dtype=torch.float32, scale=ones, shift=shift, residual=res, relu=False, tile=False)
-            hi, lo = S.split_bf16_add(y, t, n, relu=True)
-            return (hi, lo, y)
-        t = S.conv_forward(x[1], whi, rb, n, out_dtype=torch.float32, residual=res, tile=False)
-        t = S.conv_forward(x[0], wlo, rb, n, out_dtype=torch.float32, residual=t, out=t, tile=False)
-        y = S.conv_forward(x[0], whi, rb, n, out_dtype=torch.float32, scale=ones, shift=shift, residual=t, relu=True, out=t if out is None else out,
-                           tile=False)
-        return self._split(y, n)
+        fast = ranked and (C in getattr(rb, "_tile_rb", {}) or (C == 128 and getattr(rb, "_sorted", None) is not None))
+        # the two cross terms are 2^-8 of the result: bf16 precision is enough for them, so they run with bf16 outputs (on the
+        # bf16 engine's tile-rulebook / class-sorted kernels where the stage has them) chained through a bf16 residual; only the
+        # main product keeps f32, and ITS epilogue adds them, applies the ReLU and writes the f32 rows with their (hi, lo) split
+        # (conv_forward_split: every layer's (Cin, Cout) is one of its shapes, _fold_x3)
+        kw = dict(ranked=True) if fast else dict(tile=False)
+        t = S.conv_forward(x[1], whi, rb, n, **kw)
+        t = S.conv_forward(x[0], wlo, rb, n, residual=t, out=t, **kw)
+        y, hi, lo = S.conv_forward_split(x[0], whi, rb, n, scale=ones, shift=shift, residual=res, addend=t, relu=True, ranked=ranked,
+                                         tile=None if fast else False, want_f32=want_f32)
+        return (hi, lo, y)
 
     # ---- persistent rank grids (zero between calls; cleared sparsely after use) -----------
     def _stage_shapes(self):
@@ -1021,26 +1002,14 @@ class FusedResBackbone:
                 self._graphs[key] = g
             g.stage(points, batch_offsets)
             g.replay(self.profile if probe else None)
-            stage, caps, shapes = g.res['stages'], g.res['caps'], g.res['shapes']
-            counts = g.counts()   # the one host sync: the counts' copy between the two graphs
-            overflow = self._ell_overflow(counts, g.res['ell_used'], caps[0])
-            self._check_aborts(counts.pop())
-            for l in range(1, 5):
-                if counts[l] > caps[l]:
-                    self.cap_factor[l - 1] = max(self.cap_factor[l - 1] * 2.0, counts[l] * 1.25 / caps[0])
-                    overflow = True
-            if not overflow:
+            counts = g.counts()   # the one host sync: the counts the graph's counts launch stored (a probe: their copy between its two graphs)
+            if not self._digest_counts(counts, g.res['ell_used'], g.res['caps']):
                 break
             torch.cuda.synchronize(points.device)                  # (the second graph of the failed forward may still be running)
             for gr in self._get_grids(batch_size, points.device):   # see _run_once: the sparse clear missed cells
                 gr.zero_()
             del self._graphs[key]                                  # recapture with the larger buffers
-        tensors = [spconv.SparseConvTensor(x[:counts[l]], idx[:counts[l]], shapes[l], batch_size, n_dev=nd)
-                   for l, (x, idx, nd, _) in enumerate(stage)]
-        n1 = counts[0]
-        return {'x_conv1': tensors[0], 'x_conv2': tensors[1], 'x_conv3': tensors[2], 'x_conv4': tensors[3],
-                'out': tensors[4], 'counts': counts, 'voxel_coords': g.vox['coords'][:n1],
-                'voxel_num_points': g.vox['num_points'][:n1], 'voxel_features': g.vox['mean'][:n1]}
+        return self._results(g.res['stages'], counts, g.res['shapes'], batch_size, vox=g.vox)
 
     def run(self, feats, indices, n1, batch_size, grid1=None, sync=True, n_cells=None, final_dtype=None):
         """feats (cap1,Cin) f32, indices (cap1,4) i32, n1 (1,) i32 device.
@@ -1081,41 +1050,30 @@ class FusedResBackbone:
             grid1 = S.build_grid(indices, n1, batch_size, m.sparse_shape, keep_order=True, grid=grids[0])
         caps = [cap1] + [max(256, int(cap1 * f)) for f in self.cap_factor]
 
+        def timed(tag, fn, *args, **kw):   # (profile: one launch between a pair of timing events; never on the unprofiled path)
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            y = fn(*args, **kw)
+            e1.record()
+            self.profile.append((tag, e0, e1))
+            return y
+
         def conv(x, prm, rb, n, residual=None, out_dtype=act, ranked=False, want_f32=True):
             if self.x3 and isinstance(prm[0], tuple):
-                return self._conv_x3(x, prm, rb, n, residual, None, ranked, want_f32)
+                return self._conv_x3(x, prm, rb, n, residual, ranked, want_f32)
             w, sc, sh = prm
             tag = (int(w.shape[2]), int(w.shape[1]), int(w.shape[0]), residual is not None, ranked)  # Cin, Cout, K, res
             if self.rulebook_log is not None:
                 self.rulebook_log.append((tag, rb, n))
             if getattr(rb, "_ell", None) is not None and (rb.nbr is None or int(w.shape[2]) <= 8):   # on the compact rulebook
-                if self.profile is None or (self.profile_only is not None and tag[:3] not in self.profile_only):
-                    return S.conv_forward_ell(x, w, rb, n, out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                y = S.conv_forward_ell(x, w, rb, n, out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True)
-                e1.record()
-                self.profile.append((tag, e0, e1))
-                return y
-            if rb.nbr is None:   # fused strided layer
-                if self.profile is None or (self.profile_only is not None and tag[:3] not in self.profile_only):
-                    return S.conv_forward_strided(x, w, rb, scale=sc, shift=sh, relu=True)
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                y = S.conv_forward_strided(x, w, rb, scale=sc, shift=sh, relu=True)
-                e1.record()
-                self.profile.append((tag, e0, e1))
-                return y
+                fn, args, kw = S.conv_forward_ell, (x, w, rb, n), dict(out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True)
+            elif rb.nbr is None:   # fused strided layer
+                fn, args, kw = S.conv_forward_strided, (x, w, rb), dict(scale=sc, shift=sh, relu=True)
+            else:
+                fn, args, kw = S.conv_forward, (x, w, rb, n), dict(out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True, ranked=ranked)
             if self.profile is None or (self.profile_only is not None and tag[:3] not in self.profile_only):
-                return S.conv_forward(x, w, rb, n, out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True,
-                                      ranked=ranked)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            y = S.conv_forward(x, w, rb, n, out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True,
-                               ranked=ranked)
-            e1.record()
-            self.profile.append((tag, e0, e1))
-            return y
+                return fn(*args, **kw)
+            return timed(tag, fn, *args, **kw)
 
         def blocks(x, rb, n, prms, ranked=False):
             for p1, p2 in prms:
@@ -1176,8 +1134,6 @@ class FusedResBackbone:
                 rb1 = S.rulebook_subm(indices, n1, grid1, 3, masks=srt1)
                 if srt1:
                     S.classsort_f32(rb1, n1, 16)
-        down_convs = (m.conv2[0][0], m.conv3[0][0], m.conv4[0][0], m.conv_out[0])
-        premarked = False     # did the previous stage's rulebook kernel mark this strided layer's output sites already?
         idx_prev, n_prev, g_prev = indices, n1, grid1
         books = []
         for li, (down_key, blk_key, dconv) in enumerate((('down2', 'blocks2', m.conv2[0][0]),
@@ -1191,7 +1147,7 @@ class FusedResBackbone:
             ell_down = ell_all and li == 0 and tuple(dconv.kernel_size) == (3, 3, 3) and (int(wd.shape[2]), int(wd.shape[1])) in S.ELL_SHAPES
             with _Index():
                 rbs = S.rulebook_strided(idx_prev, n_prev, g_prev, dconv.kernel_size, dconv.stride, dconv.padding,
-                                         caps[li + 1], out_grid=grids[li + 1], want_nbr=not (fused or ell_down), premarked=premarked)
+                                         caps[li + 1], out_grid=grids[li + 1], want_nbr=not (fused or ell_down))
                 if ell_down:
                     S.ell_for_strided(rbs, int(caps[li + 1] * self.ell_pool[1]) + 64, used=self._ell_counter(1, dev))
                     ell_used.append((rbs._ell[2], rbs._ell[1], 1))
@@ -1199,24 +1155,19 @@ class FusedResBackbone:
                 # rulebook (stage 2, 32 channels), the rulebook kernel writes it in the same pass
                 w0 = P[blk_key][0][0][0]
                 ch = int((w0[0] if isinstance(w0, tuple) else w0).shape[1])
-                act_k = torch.bfloat16 if (self.x3 and X3_FAST) else act     # (bf16x3: its cross terms run on the bf16 engine's kernels)
+                act_k = torch.bfloat16 if self.x3 else act     # (bf16x3: its cross terms run on the bf16 engine's kernels)
                 srt = S.sorted_by_default(ch, ch, act_k, caps[li + 1])
                 tiled = (S.tiled_by_default(ch, act_k, caps[li + 1]) and S.tiled_fits(caps[li + 1], ch, caps[li + 1], caps[li + 1])
                          and self.tile_off.get(li, 0) <= 0)
-                # the SubM rulebook kernel of this stage also marks the output sites of the NEXT strided layer (the coordinates are
-                # in its registers): that layer's own marking launch goes
-                nxt = down_convs[li + 1]
-                lean = tiled and self.rulebook_log is None and (not self.x3 or (X3_FAST and X3_FUSED))   # (all four layers of the stage run tiled)
-                mark_next = (grids[li + 2], nxt.kernel_size, nxt.stride, nxt.padding) if (lean or srt) and S.MARK_FUSED else None
+                lean = tiled and self.rulebook_log is None   # (all four layers of the stage run tiled)
                 srt32 = S.f32_sorted_by_default(ch, act, caps[li + 1]) and self.rulebook_log is None and not self.x3
                 esc_ctr = self._ell_counter(("esc", li), dev) if (lean and S.TILE_MODE is None) else None
                 rb = S.rulebook_subm(rbs.out_indices, rbs.out_n, rbs.out_grid, 3, tile_channels=ch if tiled else None, masks=srt or srt32,
-                                     lean_table=lean, mark_next=mark_next, esc_counter=esc_ctr)
+                                     lean_table=lean, esc_counter=esc_ctr)
                 if esc_ctr is not None:
                     ell_used.append((esc_ctr, None, ("esc", li)))
                 if self.tile_off.get(li, 0) > 0:
                     rb._no_tile = True
-                premarked = bool(getattr(rb, "_marked_next", False))
                 if srt:
                     S.classsort(rb, rbs.out_n, ch)   # stage 4: the 128-channel layers sweep their rows class by class
                 if srt32:
@@ -1229,14 +1180,14 @@ class FusedResBackbone:
         # strided layer of stage 4: the host has its counts after ~half of a one-scene forward and sizes the outputs, returns, and
         # issues the next frame while the convolutions still run.  (What is not final there is the tiled kernels' time-out counter: in
         # this form a time-out — never seen; the protocol's guard against a hang — raises with the NEXT forward's counts.)
-        early_counts = probe is not None and getattr(probe, "host_counts", False)
+        early_counts = probe is not None and probe.host_counts
         counts_box = {}
+        count_srcs = lambda: [(None, None, n1)] + [(None, None, b[2].out_n) for b in books] + [(None, None, rbo.out_n)]
         with _Index():
             rbo = S.rulebook_strided(idx_prev, n_prev, g_prev, oconv.kernel_size, oconv.stride, oconv.padding, caps[4],
-                                     out_grid=grids[4], premarked=premarked)
+                                     out_grid=grids[4])
             if early_counts:
-                srcs = [(None, None, n1)] + [(None, None, b[2].out_n) for b in books] + [(None, None, rbo.out_n)]
-                counts_box['dev'] = self._counts_word(srcs, ell_used, dev, host=probe.counts_host())
+                counts_box['dev'] = self._counts_word(count_srcs(), ell_used, dev, host=(probe.counts_pin, probe.counts_seq))
                 probe.counts_ready(counts_box['dev'])
 
         # ---- convolutions -----------------------------------------------------------------------------------------------
@@ -1296,10 +1247,9 @@ class FusedResBackbone:
         def counts_now():
             if early_counts:
                 return
-            srcs = [(None, None, n1)] + [(None, None, b[2].out_n) for b in books] + [(None, None, rbo.out_n)]
-            cd = counts_box['dev'] = self._counts_word(srcs, ell_used, dev, host=probe.counts_host() if probe is not None else None)
+            cd = counts_box['dev'] = self._counts_word(count_srcs(), ell_used, dev)
             if probe is not None:
-                probe.counts_ready(cd)          # (_PointsGraph: the first captured graph ends here)
+                probe.counts_ready(cd)          # (a probe _PointsGraph: the first captured graph ends here)
             elif sync:
                 pin = self._counts_pin
                 if pin is None or pin.numel() < cd.numel():
@@ -1354,13 +1304,7 @@ class FusedResBackbone:
             return {'stages': stage, 'shapes': shapes, 'caps': caps, 'batch_size': batch_size, 'counts_dev': counts_dev, 'ell_used': ell_used}
         counts_box['ev'].synchronize()   # the one host sync: the counts' copy, not the end of the forward
         counts = self._counts_pin[:counts_dev.numel()].tolist()
-        overflow = self._ell_overflow(counts, ell_used, cap1)
-        self._check_aborts(counts.pop())
-        for l in range(1, 5):
-            if counts[l] > caps[l]:
-                self.cap_factor[l - 1] = max(self.cap_factor[l - 1] * 2.0, counts[l] * 1.25 / cap1)
-                overflow = True
-        if overflow:
+        if self._digest_counts(counts, ell_used, caps):
             # rows beyond a capacity were never emitted, so the sparse clear missed their cells:
             # wipe the persistent grids before the retry with larger buffers
             for g in grids:
@@ -1370,15 +1314,4 @@ class FusedResBackbone:
                 self._last_done = torch.cuda.Event()     # (a caller on another stream must come behind the wipe too)
                 self._last_done.record()
             return None
-        tensors = []
-        for l, (x, idx, n, g) in enumerate(stage):
-            c = counts[l]
-            tensors.append(spconv.SparseConvTensor(x[:c], idx[:c], shapes[l], batch_size, n_dev=n))
-        return {'x_conv1': tensors[0], 'x_conv2': tensors[1], 'x_conv3': tensors[2], 'x_conv4': tensors[3],
-                'out': tensors[4], 'counts': counts}
-
-
-def _with_perm(grid, cap, device):
-    if grid.perm is None or grid.perm.numel() < cap:
-        grid.perm = torch.empty((cap,), dtype=torch.int32, device=device)
-    return grid
+        return self._results(stage, counts, shapes, batch_size)

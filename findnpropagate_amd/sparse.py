@@ -506,7 +506,9 @@ def rulebook_subm(indices, n_dev, grid, ksize, tile_channels=None, masks=False, 
     esc_counter (with lean_table): a (1,) int32 device counter that receives += the number of 32-row groups with an escape entry.
     mark_next (with lean_table or masks): (out_grid, ksize, stride, padding) of the strided convolution that consumes these rows —
     the kernel marks its output sites in out_grid (all zero) on the way; rulebook_strided(..., premarked=True) then skips its
-    own marking launch.  `rb._marked_next` says whether it was done."""
+    own marking launch.  `rb._marked_next` says whether it was done.  Built and tested, but the fused engine does not use it:
+    measured -1.1 % end to end at 64 scenes (the atomics' dependent chain lengthens every pass of the rulebook kernels, which the
+    stand-alone marking launch hides behind a grid of its own with the next row's coordinates prefetched)."""
     L = _l.load()
     cap = max(indices.shape[0], 1)
     geom, _ = make_geom(ksize, 1, [k // 2 for k in _triple(ksize)], grid.shape, grid.shape)
@@ -520,7 +522,7 @@ def rulebook_subm(indices, n_dev, grid, ksize, tile_channels=None, masks=False, 
             mg = out_grid.c(with_perm=False)
         else:
             mgeom = None
-    if tile_channels and K == 27 and os.environ.get("FNP_TILE_FUSED", "1") != "0":   # (0: development A/B — the stand-alone build on first use)
+    if tile_channels and K == 27:
         t = torch.empty((L.fnp_tile_rulebook_bytes(cap, tile_channels),), dtype=torch.uint8, device=indices.device)
         if lean_table:
             rc = L.fnp_rulebook_subm_tiled_lean(_l.ptr(indices), _l.ptr(n_dev), cap, geom, grid.c(), _l.ptr(nbr), tile_channels, _l.ptr(t), mg, mgeom,
@@ -684,7 +686,7 @@ def tiled_fits(n_in_rows, channels, nbr_stride, cap_out):
 
 # ... and the ones that take it by themselves (measured at 64 scenes, per layer: 32 channels 0.305 -> 0.18 ms; 64 channels
 # 0.43 -> 0.385 ms, +1 % end to end)
-TILED_AUTO = tuple(int(v) for v in os.environ.get("FNP_TILED_AUTO", "32,64").split(",") if v)   # (development A/B: e.g. FNP_TILED_AUTO=32)
+TILED_AUTO = (32, 64)
 
 
 # --------------------------------------------------------------------------------- compact rulebook (sparse-neighbourhood layers)
@@ -753,20 +755,13 @@ def conv_forward_ell(feat_in, w_packed, rb, n_out_dev, out_dtype=None, scale=Non
     return out
 
 
-# the next stage's output sites marked by this stage's rulebook kernel (rulebook_subm(mark_next=...)): built and tested, OFF by
-# default — measured -1.1 % end to end at 64 scenes (the atomics' dependent chain lengthens every pass of the rulebook kernels,
-# which the stand-alone marking launch hides behind a grid of its own with the next row's coordinates prefetched)
-MARK_FUSED = os.environ.get("FNP_MARK_FUSED", "0") == "1"
 SORTED_SHAPES = {(128, 128)}   # (Cin, Cout) fnp_spconv_forward_sorted covers
-# the class-sorted sweep pays from a few scenes on (one more small kernel per forward against ~20 % of four sweeps); 0 / 1 force it
-SORT_MODE = {"0": False, "1": True}.get(os.environ.get("FNP_SORT", ""))
+# the class-sorted sweep pays from a few scenes on (one more small kernel per forward against ~20 % of four sweeps)
 SORT_MIN_ROWS = 131072   # (row CAPACITY of the stage: a one-scene hipGraph has 65,536; from ~4 scenes on the sort pays)
 
 
 def sorted_by_default(cin, cout, dtype, cap):
-    if (cin, cout) not in SORTED_SHAPES or dtype not in (torch.bfloat16, torch.float16):
-        return False
-    return bool(SORT_MODE) if SORT_MODE is not None else cap >= SORT_MIN_ROWS
+    return (cin, cout) in SORTED_SHAPES and dtype in (torch.bfloat16, torch.float16) and cap >= SORT_MIN_ROWS
 
 
 def classsort(rb, n_out_dev, channels=128):
@@ -792,14 +787,13 @@ def classsort(rb, n_out_dev, channels=128):
 
 
 # f32 engine: the 3x3x3 SubM layers sweep every workgroup range class by class (the f32 kernel is bound by the matrix pipe and
-# skips the MFMAs of a 16-row block at offsets none of its rows has a neighbour at).  FNP_F32_SORT=0: row order (development A/B)
-F32_SORT = os.environ.get("FNP_F32_SORT", "1") != "0"
+# skips the MFMAs of a 16-row block at offsets none of its rows has a neighbour at)
 F32_SORT_CHANNELS = {16, 32, 64, 128}
-F32_SORT_MIN_ROWS = int(os.environ.get("FNP_F32_SORT_MIN_ROWS", "32768"))
+F32_SORT_MIN_ROWS = 32768
 
 
 def f32_sorted_by_default(channels, dtype, cap):
-    return F32_SORT and dtype == torch.float32 and channels in F32_SORT_CHANNELS and cap >= F32_SORT_MIN_ROWS
+    return dtype == torch.float32 and channels in F32_SORT_CHANNELS and cap >= F32_SORT_MIN_ROWS
 
 
 def classsort_f32(rb, n_out_dev, channels):
@@ -979,7 +973,7 @@ def conv_forward_strided(feat_in, w_packed, rb, scale=None, shift=None, relu=Fal
 
 # layers the fused backbone runs this way (16 -> 32 is built and tested too, but measured 2.5 % slower end to end than its table
 # path: its input grid carries the voxeliser's permutation and its LDS strip costs a resident workgroup)
-FUSED_STRIDED_SHAPES = {(32, 64), (64, 128)} | ({(16, 32)} if os.environ.get("FNP_FUSED1632") == "1" else set())   # (development switch)
+FUSED_STRIDED_SHAPES = {(32, 64), (64, 128)}
 
 
 # --------------------------------------------------------------------------------- backward
@@ -1014,7 +1008,6 @@ def conv_dgrad(grad_out, w_packed, nbr_t, n_in_dev, cap_in, pretransposed=False)
 
 
 WGRAD_PAIR_SHAPES = {(16, 16), (16, 32), (32, 32), (32, 64), (64, 64), (64, 128), (128, 128)}   # (Cin, Cout) of the MFMA weight gradient
-WGRAD_PAIRS = os.environ.get("FNP_WGRAD_PAIRS", "1") == "1"
 
 
 def mfma_pad_channels(cin, cout):
@@ -1061,7 +1054,7 @@ def conv_wgrad(feat_in, grad_out, rb, n_out_dev, Cin, Cout, pairs=None, module_s
     dw = torch.empty((rb.K, Cout, Cin) if module_shape is None else tuple(module_shape), dtype=torch.float32, device=feat_in.device)
     ws = torch.empty((int(L.fnp_spconv_wgrad_workspace_bytes(rb.K, Cin, Cout)),), dtype=torch.uint8, device=feat_in.device)
     cap = min(rb.cap_out, grad_out.shape[0])
-    use_pairs = WGRAD_PAIRS if pairs is None else pairs
+    use_pairs = pairs is None or pairs
     mfma_pairs = (Cin, Cout) in WGRAD_PAIR_SHAPES and feat_in.dtype in (torch.bfloat16, torch.float16) and grad_out.dtype == feat_in.dtype
     small_pairs = Cin * Cout <= 128 and feat_in.dtype == torch.float32 and grad_out.dtype == torch.float32   # (conv_input: 3.6 of 27 neighbours per row)
     if use_pairs and (mfma_pairs or small_pairs) and rb.nbr is not None and not getattr(rb, "_lean", False):
