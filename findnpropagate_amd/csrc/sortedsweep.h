@@ -84,3 +84,9 @@ constexpr int kSortedNW = 8, kSortedMB = 3;
 __attribute__((visibility("hidden"))) int fnp_launch_rows128(int dtype, const void *x, const void *w, const int *nbr, int nbr_stride, const int *n_out,
                                                              int cap, void *y, const float *scale, const float *shift, const void *residual, int relu,
                                                              const int *perm, const unsigned *blockmask, int grid, hipStream_t s);
+
+// spconv_out128.hip: a 128 -> 128 convolution of three kernel offsets (conv_out), 16-bit in, 16-bit (out_f32 == 0: the input's type) or f32
+// out, no residual, with the three weight slabs resident in LDS.  Library-internal (not part of the C ABI).
+__attribute__((visibility("hidden"))) int fnp_launch_out128(int in_dtype, int out_f32, const void *x, int x_bytes, const void *w, const int *nbr,
+                                                            int nbr_stride, const int *n_out, int cap, void *y, const float *scale, const float *shift,
+                                                            int relu, hipStream_t s);

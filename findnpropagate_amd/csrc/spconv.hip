@@ -1213,12 +1213,29 @@ __global__ __launch_bounds__(kSortThreads) void classsort_place_kernel(const uns
     }
 }
 
+// capacity from which conv_out's shape takes spconv_out128_kernel: 256 workgroups x 8 waves x two 32-row tiles.  Measured on the
+// conv_out table of a 128-scene batch cut to a prefix (tools/ab_conv_out.py, f32 out, generic / new in us, one run,
+// profiles/r08_ab_conv_out_b128.json): 96 k rows 22.4 / 25.7, 128 k 29.2 / 28.8, 192 k 39.9 / 38.3, 256 k 53.4 / 46.7, 878 k (the whole
+// layer) 213.2 / 172.9.  The threshold sits at PARITY (at 128 k the two are within the run's noise; the new kernel is clearly ahead
+// from 192 k on, clearly behind at 96 k and below: the one-off staging of the three slabs and idle waves outweigh the barrier-free
+// loop there).  tests/test_gpu_conv_out.py restates the value (OUT128_MIN_CAP) for its cases on either side: move both together.
+// (FNP_OUT128_MIN_CAP: development builds that time the two kernels on either side of it)
+#ifndef FNP_OUT128_MIN_CAP
+#define FNP_OUT128_MIN_CAP (256 * 8 * 64)
+#endif
+constexpr int kOut128MinCap = FNP_OUT128_MIN_CAP;
+
 template <typename TAct, typename TOut>
 int dispatch_16(const void *x, long long n_in, const void *w, const int *nbr, int nbr_stride, int K, const int *n_out, int cap,
                   void *y, const float *scale, const float *shift, const void *residual, int relu, int hints, int Cin,
                   int Cout, hipStream_t s, const SplitOut *so = nullptr) {
     const long long xb = n_in * Cin * 2;
     const bool fits = xb > 0 && xb < 0x7fffffffll;   // 32-bit buffer offsets of the MFMA path
+    // conv_out (128 -> 128, three offsets, no residual): the kernel with resident slabs and independent waves (spconv_out128.hip),
+    // from the capacity at which it is the faster one (kOut128MinCap); same bits as the generic kernel below
+    if (fits && K == 3 && Cin == 128 && Cout == 128 && !residual && !so && cap >= kOut128MinCap)
+        return fnp_launch_out128(std::is_same<TAct, __bf16>::value ? FNP_BF16 : FNP_F16, sizeof(TOut) == 4, x, (int)xb, w, nbr, nbr_stride, n_out, cap, y,
+                                 scale, shift, relu, s);
 #define FNP_CASE(CI, CO)                                                                                       \
     if (fits && Cin == CI && Cout == CO)                                                                       \
         return launch_mfma<CI, CO, TOut, TAct>(x, (int)xb, w, nbr, nbr_stride, K, n_out, cap, y, scale, shift, residual,\

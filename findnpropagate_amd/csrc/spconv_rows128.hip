@@ -26,11 +26,15 @@
 //     5. s_barrier: every wave's slab pieces of step s + 1 are in; every wave is done reading ring slot s mod 3
 //   The count in 3 is exact because a wave issues NOTHING else on the vector-memory queue inside the sweep: rulebook entries come by
 //   LDS-DMA too and are read back with ds_read (an ordinary load beside LDS-DMA in flight makes the compiler wait vmcnt(0) at its
-//   use).  The wait is vmcnt(0) only in the two steps of a tile's last offset, where nothing younger exists.  Slabs are read one phase
+//   use).  The wait is vmcnt(0) only in the two steps of a tile's last offset, where no piece is issued: those two steps are peeled off
+//   the loop, and ahead of them go the ordinary loads of what the epilogue starts with — the rows behind the wave's positions (perm) and
+//   the next tile's block masks and entry row — so that they land under the 48 MFMAs of the first of the two steps (its vmcnt(0)
+//   retires them; their first use is the epilogue, another 48 MFMAs on) instead of standing at the epilogue's top (a load there
+//   breaks no count: nothing has to stay in flight across these waits).  Slabs are read one phase
 //   after the wait that retires them (the barrier of 5 lies between); a buffer is restaged only after an lgkmcnt(0) (rows: the wave's
 //   own reads) or a barrier (slabs: every wave's reads).  No __syncthreads() in the sweep: its fence would drain the prefetch.
 //   What a tile needs before its first piece (live offsets, perm rows, the entries of its first two offsets: three dependent trips to
-//   HBM) is fetched inside the epilogue of the tile before (TileSt below).
+//   HBM) is fetched by the tile before: the first two in its last offset, the entries at the top of its epilogue (TileSt below).
 //
 // LDS images are lane-linear per piece (the DMA writes base + lane * 16), so the XOR swizzle that makes the fragment reads
 // conflict-free is applied to the SOURCE address: slot r (128 bytes: row r of a row buffer, output channel r of a half slab) holds
@@ -116,9 +120,9 @@ __global__ __launch_bounds__(kR128NT, 2) void spconv_rows128_kernel(const TAct *
 
     // What a tile's sweep needs before its first piece can go out — the live offsets (Kt of them; lane l of kl holds the l-th) and the row
     // behind the position whose rulebook ENTRY this lane fetches — comes from two cold lines (blockmask, perm), and the entries of the first
-    // two offsets from a third: three dependent round trips to HBM.  They are made for tile t + 1 inside the epilogue of tile t
-    // (tile_loads beside its perm loads, tile_state + the two entry DMAs beside its residual loads), so that a tile's prologue waits for
-    // its first rows only.  `mbt`: 16-position blocks per wave of the tile (MB; fewer in the partial round).
+    // two offsets from a third: three dependent round trips to HBM.  They are made for tile t + 1 by tile t: tile_loads at the
+    // top of its last offset, beside its own perm loads; tile_state + the two entry DMAs at the top of its epilogue, beside its residual
+    // loads — so that a tile's prologue waits for its first rows only.  `mbt`: 16-position blocks per wave of the tile (MB; fewer in the partial round).
     // Piece ii of a step fetches positions 8 ii + r8; the entry of position 8 ii + r8 is held by lane 2 ii + (r8 & 1) of the 16-lane row
     // r8 >> 1: lane (r4, c16), c16 < 4 mbt, holds position 8 (c16 >> 1) + 2 r4 + (c16 & 1).
     struct TileSt {
@@ -204,10 +208,12 @@ __global__ __launch_bounds__(kR128NT, 2) void spconv_rows128_kernel(const TAct *
 #pragma unroll
             for (int mb = 0; mb < MBT; ++mb) acc[nb][mb] = (f32x4){0.f, 0.f, 0.f, 0.f};
 
-        // one step: see the head of the file.  `more`: the tile has another offset behind this one (uniform).  On entry the step's B
+        // one step: see the head of the file.  `more`: the tile has another offset behind this one (a constant: the sweep's last offset is
+        // peeled off the loop).  On entry the step's B
         // fragments are on their way to xb (read behind the wait of the step before: the rows are the wave's own).
-        auto step = [&](auto half_tag, const int k, const bool more, const int e_next, const int ring_s, const int ring_s2) {
+        auto step = [&](auto half_tag, auto more_tag, const int k, const int e_next, const int ring_s, const int ring_s2) __attribute__((always_inline)) {
             constexpr int half = decltype(half_tag)::value;
+            constexpr bool more = decltype(more_tag)::value;
             constexpr int NG = 4, SLOTS = NG * MBT, NP = NROW + NSLAB + 1;   // a slot = 4 MFMAs; the NP pieces are spread evenly over the slots
             const unsigned char *wk = fnp_smem + ring_s * kR128Slab;
             const int ev = ehas ? e_next : -1;
@@ -273,14 +279,28 @@ __global__ __launch_bounds__(kR128NT, 2) void spconv_rows128_kernel(const TAct *
         __builtin_amdgcn_sched_barrier(0);
         __builtin_amdgcn_s_barrier();
         __builtin_amdgcn_sched_barrier(0);
+        // What the epilogue needs from two cold lines — the rows behind the positions this lane stores (orow) and the next tile's block
+        // masks and entry row (tile_loads) — is requested at the top of the tile's LAST offset: its two steps issue no piece and wait
+        // vmcnt(0) anyway, so an ordinary load there breaks no count, and the epilogue starts with its addresses in registers.
+        // (one register across the sweep's last steps, not twelve: lane l fetches the row behind position row0 + l, and the epilogue
+        //  hands the rows to the lanes that store them with a lane exchange)
+        int prow = 0;
+        unsigned nm = 0u;
+        int nerow = 0;
         int ring = 0;   // ring slot of step 2 k
-        for (int k = 0; k < Kt; ++k) {
-            const bool more = k + 1 < Kt;
+        for (int k = 0; k + 1 < Kt; ++k) {
             const int r1 = ring == 2 ? 0 : ring + 1, r2 = r1 == 2 ? 0 : r1 + 1;
-            const int e_next = read_ent((k + 1) & 1);   // entries of offset k + 1 (landed a step ago; unused when there is none)
-            step(std::integral_constant<int, 0>{}, k, more, e_next, ring, r2);
-            step(std::integral_constant<int, 1>{}, k, more, e_next, r1, ring);
+            const int e_next = read_ent((k + 1) & 1);   // entries of offset k + 1 (landed a step ago)
+            step(std::integral_constant<int, 0>{}, std::true_type{}, k, e_next, ring, r2);
+            step(std::integral_constant<int, 1>{}, std::true_type{}, k, e_next, r1, ring);
             ring = r2;
+        }
+        {   // the last offset (Kt >= 1)
+            const int r1 = ring == 2 ? 0 : ring + 1, r2 = r1 == 2 ? 0 : r1 + 1;
+            if (next_mbt) tile_loads(next_base, next_mbt, nm, nerow);   // (uniform)
+            prow = srb.perm[min(row0 + lane, row_end - 1)];
+            step(std::integral_constant<int, 0>{}, std::false_type{}, Kt - 1, 0, ring, r2);
+            step(std::integral_constant<int, 1>{}, std::false_type{}, Kt - 1, 0, r1, ring);
         }
 
         // epilogue (spconv_mfma_kernel's wide form: a 16-site block transposed through a wave-private strip, 16 bytes per lane over whole
@@ -290,16 +310,10 @@ __global__ __launch_bounds__(kR128NT, 2) void spconv_rows128_kernel(const TAct *
         const int wsite = lane / LPR, wchunk = lane % LPR;
         u32x4 rs_all[MBT][NRD];
         int orow[MBT][NRD];
-        unsigned nm = 0u;
-        int nerow = 0;
-        if (next_mbt) tile_loads(next_base, next_mbt, nm, nerow);   // (uniform)
 #pragma unroll
         for (int mb = 0; mb < MBT; ++mb)
 #pragma unroll
-            for (int i = 0; i < NRD; ++i) {
-                const int r = row0 + mb * 16 + i * SPI + wsite;
-                orow[mb][i] = srb.perm[r < row_end ? r : row_end - 1];
-            }
+            for (int i = 0; i < NRD; ++i) orow[mb][i] = __shfl(prow, mb * 16 + i * SPI + wsite);   // (positions past the range: the last row's)
         TileSt nst{1, 13, 0};
         if (next_mbt) {   // the next tile's first entries fly while this one's outputs are made (the entry slots are free: the sweep is over)
             nst = tile_state(nm, nerow);
