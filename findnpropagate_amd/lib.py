@@ -203,6 +203,11 @@ SIGNATURES = {
     "fnp_heatmap_loss_workspace_bytes": (c_int64, [c_int64]),
     "fnp_heatmap_loss_forward": (c_int, [P, c_int, P, c_int64, P, P, c_int64, P, P]),
     "fnp_heatmap_loss_backward": (c_int, [P, c_int, P, c_int64, P, P, P, P]),
+    "fnp_proposals_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int, c_int]),
+    "fnp_proposals": (c_int, [P, c_int, c_int, c_int, c_int, c_int, c_int, c_uint64, P, c_int64, P, P, P, P, P]),
+    "fnp_query_init": (c_int, [P, P, c_int, P, P, P, P, c_int, c_int, c_int64, c_int, c_int, P, P, P]),
+    "fnp_tf_decode": (c_int, [P, P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_float, c_float, c_float, c_float, c_float,
+                              c_float, c_uint64, POINTER(c_float), P, P, P, P, P, P]),
 }
 
 

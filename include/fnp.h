@@ -847,6 +847,57 @@ int fnp_heatmap_loss_forward(const void *logits, int dtype, const float *target,
 int fnp_heatmap_loss_backward(const void *logits, int dtype, const float *target, int64_t n, const int *num_pos,
                               const float *grad_out, void *grad_logits, fnp_stream_t stream);
 
+/* Inference side of TransFusionHead around its decoder (transfusion_head.py:201-324 and :616-728; additive, ABI 14).  Every
+ * call takes a stream, allocates nothing and does not synchronise; all tensors are f32 unless stated.
+ *
+ * fnp_proposals: heatmap (B, C, H, W), logits when from_logits != 0 (the sigmoid is fused: 1.0f / (1.0f + expf(-x)), not
+ * contracted, no fast-math) and probabilities >= 0 otherwise -> top_class, top_index (B, K) int64, top_score (B, K) and
+ * query_heatmap_score (B, C, K).  1 <= C <= 64, 1 <= K <= min(2048, C*H*W), C*H*W < 2^31.
+ *   1. Masked value.  s = the probability.  An ordinary class keeps s at an interior cell where s equals the maximum of its
+ *      3 x 3 neighbourhood, and is 0 elsewhere, border cells included (NMS_KERNEL_SIZE is 3; the caller asserts it).
+ *   2. Point classes, bit c of point_class_mask, keep s at every cell, border included.
+ *   3. Order: masked value descending, then flat index c*H*W + h*W + w ascending.  The reference's argsort is not stable, so
+ *      among tied values the rule is this library's; where values are distinct it is the reference's order.
+ *   4. Zero fill.  Masked-out cells take part with value 0: with P < K positive cells, the remaining K - P places go to the
+ *      lowest flat indices that are no positive cell, ascending (all of them below K).
+ *   5. top_class = flat / (H*W), top_index = flat % (H*W), top_score = the masked value.
+ *   6. query_heatmap_score[b, c, k] = the masked value of class c at top_index[b, k], from the same device function as the
+ *      selecting pass.
+ *   7. Finite values and +-inf are in contract; NaN is out of contract (a NaN cell is never selected as positive, and may
+ *      spoil its neighbours' maxima).  Results are bit-identical from run to run.
+ * workspace: fnp_proposals_workspace_bytes(B, C, H, W, K) bytes, 8-byte aligned (negative: the shape is out of contract).
+ *
+ * fnp_query_init: query_feat[b, f, k] = lidar_feat[b, f, top_index[b, k]] + (enc_weight[f, top_class[b, k]] + enc_bias[f]),
+ * in that association (the one-hot Conv1d class encoding), and query_pos[b, k, :] = bev_pos[top_index[b, k], ::-1], gathered
+ * from the caller's table: bev_pos is (num_cells, 2), or (B, num_cells, 2) when bev_pos_batched != 0.  lidar_feat
+ * (B, F, num_cells), F >= 2; enc_weight (F, C); outputs (B, F, K) and (B, K, 2).  An index or class outside its range yields
+ * NaN and is never followed.
+ *
+ * fnp_tf_decode: get_bboxes + decode_bbox(filter=True).  heatmap (logits) and query_heatmap_score (B, C, K), center (B, 2, K),
+ * height (B, 1, K), dim (B, 3, K), rot (B, 2, K: sin, cos), vel (B, 2, K) or NULL, query_labels (B, K) int64.  Per query, with
+ * q = query_labels[b, k]: v = sigmoid(heatmap[b, q, k]) * query_heatmap_score[b, q, k]; label = q when v > 0, else 0 (the
+ * reference's maximum over an all-zero column); x = center_x * stride * voxel_x + range_x in f32, two multiplications and
+ * one addition, not contracted (y alike); z = height; sizes exp(dim); yaw atan2(sin, cos); the score, the sizes and the yaw
+ * are formed in f64 and rounded once to f32 (closer to the true value than expf / atan2f).  A query is kept when
+ * score > score_thresh (score_thresh_unk when bit `label` of unknown_mask is set, i.e. the 1-based label is an unknown
+ * class) and post_center_range[0:3] <= (x, y, z) <= post_center_range[3:6] (a HOST array of 6 floats), all in f32.  Kept rows are written
+ * per scene in query order: boxes (B, K, 7 or 9), scores (B, K), labels (B, K) int32 = label + 1, mapped through relabel
+ * (C + 1 int32 on the device, or NULL); counts (B) int32; the rows behind a scene's count are zero. */
+int64_t fnp_proposals_workspace_bytes(int batch_size, int num_classes, int height, int width, int num_proposals);
+int fnp_proposals(const float *heatmap, int batch_size, int num_classes, int height, int width, int num_proposals,
+                  int from_logits, uint64_t point_class_mask, void *workspace, int64_t workspace_bytes, int64_t *top_class,
+                  int64_t *top_index, float *top_score, float *query_heatmap_score, fnp_stream_t stream);
+int fnp_query_init(const float *lidar_feat, const float *bev_pos, int bev_pos_batched, const float *enc_weight,
+                   const float *enc_bias, const int64_t *top_class, const int64_t *top_index, int batch_size, int num_features,
+                   int64_t num_cells, int num_classes, int num_proposals, float *query_feat, float *query_pos,
+                   fnp_stream_t stream);
+int fnp_tf_decode(const float *heatmap, const float *query_heatmap_score, const float *center, const float *height,
+                  const float *dim, const float *rot, const float *vel, const int64_t *query_labels, int batch_size,
+                  int num_classes, int num_proposals, int feature_map_stride, float voxel_x, float voxel_y, float range_x,
+                  float range_y, float score_thresh, float score_thresh_unk, uint64_t unknown_mask,
+                  const float *post_center_range, const int *relabel, float *boxes, float *scores, int *labels, int *counts,
+                  fnp_stream_t stream);
+
 /* Capacity overflow: data-dependent counts (n_voxels, n_out) always hold the TRUE count; every
  * kernel clamps to the capacity it was given, so a count larger than its capacity means rows
  * were dropped and the caller must re-run with larger buffers. */
