@@ -1,5 +1,13 @@
-"""pcdet/models/model_utils/transfusion_utils.py:5-7 with the reference's signature (plain torch)."""
+"""pcdet/models/model_utils/transfusion_utils.py with the reference's signatures: clip_sigmoid (:5-7), PositionEmbeddingLearned
+(:10-26) and TransformerDecoderLayer (:29-101).  The modules keep the reference's submodule and parameter names, so a
+reference checkpoint's `decoder.*` keys load with strict=True.
+
+TransformerDecoderLayer.forward runs on the library's kernels (csrc/tfdecoder.hip, seven launches, eight with more than 256 queries, nothing read on the host)
+when plain_reasons() finds nothing against it; otherwise it is forward_plain, the reference's own torch ops with dropout and
+gradients, so training is unchanged."""
 import torch
+import torch.nn.functional as F
+from torch import nn
 
 
 def clip_sigmoid(x, eps=1e-4):
@@ -7,3 +15,91 @@ def clip_sigmoid(x, eps=1e-4):
     utils.loss_utils.heatmap_loss, the fused path, leaves its logits alone."""
     y = torch.clamp(x.sigmoid_(), min=eps, max=1 - eps)
     return y
+
+
+class PositionEmbeddingLearned(nn.Module):
+    """Learned absolute position embedding: positions (B, P, input_channel) -> (B, num_pos_feats, P) through
+    Conv1d, BatchNorm1d, ReLU, Conv1d (1-wide), held as `position_embedding_head`."""
+
+    def __init__(self, input_channel, num_pos_feats=288):
+        super().__init__()
+        layers = [nn.Conv1d(input_channel, num_pos_feats, 1), nn.BatchNorm1d(num_pos_feats), nn.ReLU(inplace=True),
+                  nn.Conv1d(num_pos_feats, num_pos_feats, 1)]
+        self.position_embedding_head = nn.Sequential(*layers)
+
+    def forward(self, xyz):
+        return self.position_embedding_head(xyz.transpose(1, 2).contiguous())
+
+
+_ACTIVATIONS = {"relu": F.relu, "gelu": F.gelu, "glu": F.glu}
+
+
+def _rows(t):
+    """(B, C, P) -> (P, B, C): nn.MultiheadAttention's sequence-first layout"""
+    return t.permute(2, 0, 1)
+
+
+class TransformerDecoderLayer(nn.Module):
+    """One post-norm decoder layer over channel-major maps: self-attention among the queries (unless cross_only), cross
+    attention of the queries over the keys, an FFN; each followed by dropout, the residual and a LayerNorm; the position
+    embeddings are added to the attention inputs (queries, keys AND values, as the reference does), not to the residual.
+
+    forward(query (B, C, Pq), key (B, C, Pk), query_pos (B, Pq, 2), key_pos (B, Pk, 2)) -> (B, C, Pq).  Submodules carry the
+    reference's names and are created in its order (so a seeded construction draws the same numbers)."""
+
+    def __init__(self, d_model, nhead, dim_feedforward=2048, dropout=0.1, activation="relu",
+                 self_posembed=None, cross_posembed=None, cross_only=False):
+        super().__init__()
+        if activation not in _ACTIVATIONS:
+            raise RuntimeError(f"activation should be relu/gelu, not {activation}.")
+        self.cross_only = cross_only
+        if not cross_only:
+            self.self_attn = nn.MultiheadAttention(d_model, nhead, dropout=dropout)
+        self.multihead_attn = nn.MultiheadAttention(d_model, nhead, dropout=dropout)
+        self.linear1, self.dropout = nn.Linear(d_model, dim_feedforward), nn.Dropout(dropout)
+        self.linear2 = nn.Linear(dim_feedforward, d_model)
+        for i in (1, 2, 3):
+            setattr(self, f"norm{i}", nn.LayerNorm(d_model))
+        for i in (1, 2, 3):
+            setattr(self, f"dropout{i}", nn.Dropout(dropout))
+        self.activation_name, self.activation = activation, _ACTIVATIONS[activation]
+        self.self_posembed, self.cross_posembed = self_posembed, cross_posembed
+        self._device_pack = None      # the device path's cached state (dense_heads.transfusion_decoder.DevicePack), made on first use
+
+    def __getstate__(self):
+        """copies, pickles and saved modules travel without the device path's cache (packed weights, the key position
+        embedding, a ctypes array): it is rebuilt on first use"""
+        state = dict(self.__dict__)
+        state["_device_pack"] = None
+        return state
+
+    def with_pos_embed(self, tensor, pos_embed):
+        return tensor if pos_embed is None else tensor + pos_embed
+
+    def plain_reasons(self, query, key, query_pos, key_pos, key_padding_mask=None, attn_mask=None):
+        """what stands against the device path, as a list of short strings (empty: the device path runs)"""
+        from ..dense_heads.transfusion_decoder import DevicePack
+
+        if self._device_pack is None:
+            self._device_pack = DevicePack(self, None)
+        return self._device_pack.reasons(query, key, query_pos, key_pos, key_padding_mask, attn_mask)
+
+    def forward(self, query, key, query_pos, key_pos, key_padding_mask=None, attn_mask=None):
+        if self.plain_reasons(query, key, query_pos, key_pos, key_padding_mask, attn_mask):
+            return self.forward_plain(query, key, query_pos, key_pos, key_padding_mask, attn_mask)
+        return self._device_pack.run(query, key, query_pos, key_pos)[0]
+
+    def forward_plain(self, query, key, query_pos, key_pos, key_padding_mask=None, attn_mask=None):
+        """the layer as torch ops, differentiable, with dropout in train(): what forward runs off the device path"""
+        q_pe = None if self.self_posembed is None else _rows(self.self_posembed(query_pos))
+        k_pe = None if self.cross_posembed is None else _rows(self.cross_posembed(key_pos))
+        x, memory = _rows(query), _rows(key)
+        if not self.cross_only:
+            a = self.with_pos_embed(x, q_pe)
+            x = self.norm1(x + self.dropout1(self.self_attn(a, a, value=a)[0]))
+        m = self.with_pos_embed(memory, k_pe)
+        attended = self.multihead_attn(query=self.with_pos_embed(x, q_pe), key=m, value=m, key_padding_mask=key_padding_mask,
+                                       attn_mask=attn_mask)[0]
+        x = self.norm2(x + self.dropout2(attended))
+        x = self.norm3(x + self.dropout3(self.linear2(self.dropout(self.activation(self.linear1(x))))))
+        return x.permute(1, 2, 0)

@@ -898,6 +898,73 @@ int fnp_tf_decode(const float *heatmap, const float *query_heatmap_score, const 
                   const float *post_center_range, const int *relabel, float *boxes, float *scores, int *labels, int *counts,
                   fnp_stream_t stream);
 
+/* TransFusionHead's decoder layer and prediction heads (transfusion_utils.py:29-101, transfusion_head.py:20-54, eval mode;
+ * additive, ABI 14; csrc/tfdecoder.hip).  All tensors f32; every product runs on the f32 MFMA (a k-ordered fmaf chain), no
+ * atomics: results are bit-identical from run to run, and a scene's result does not depend on the batch around it.  Every call
+ * takes a stream, allocates nothing and does not synchronise.  Pointers are 16-byte aligned.
+ *
+ * fnp_tf_attention: q (B, Kq, 128), k and v (B, N, 128) row-major -> out (B, Kq, 128), eight heads, head h = columns
+ * 16h .. 16h + 15, scores 0.25 * (q . k) (q is scaled first; the factor is exact), softmax over the N keys, before any output
+ * projection.  1 <= Kq <= 2048, 1 <= N < 2^31 / 128, finite inputs.
+ *   1. Geometry (fnp_tf_attention_geometry, a function of N alone): tile_len = 64;
+ *      split_len = max(256, 64 * ceil(ceil(N / 64) / 64)); split s holds keys [s * split_len, min(N, (s + 1) * split_len)).
+ *      N = 32 400 gives 64 splits of 512, i.e. 8 heads x 64 = 512 workgroups per scene, two per CU; N <= 256 is one split.
+ *   2. One workgroup per (split, head, scene x query chunk: 256 queries, 64 when N <= 256 makes one split) walks its keys in tiles of tile_len with the online softmax:
+ *      per tile m' = max(m, tile maximum), acc = acc * exp(m - m') + sum_k exp(s_k - m') v_k, l alike; exp is expf.
+ *   3. With more than one split the partials (m, l, 16 accumulators) per (scene, split, head, query) go to the workspace and
+ *      a second launch merges them in split order: M = max m_s, out = (sum_s acc_s exp(m_s - M)) / (sum_s l_s exp(m_s - M)).
+ *      With one split the first launch divides and writes out itself.
+ *   4. A query whose scores are all equal gets the mean of v; a score that leads the others by more than 104 gets that key's
+ *      v row bit for bit (exp of the difference is 0 in f32).
+ * workspace: fnp_tf_attention_workspace_bytes(B, Kq, N) bytes (0 with one split; negative: the shape is out of contract).
+ *
+ * fnp_tf_decoder: the whole forward in seven launches (front, self-attention, mid, kv_proj, cross-attention, merge, tail) for
+ * K <= 256 and eight for 256 < K <= 2048, where the self-attention has several splits and a merge launch of its own.
+ * query_feat (B, 128, K) and lidar_feat (B, 128, N) channel-major as the head holds them, query_pos (B, K, 2), key_pe (128, N)
+ * = cross_posembed(bev_pos), channel-major, or (B, 128, N) when key_pe_batched != 0 (it depends on weights and bev_pos only: the
+ * caller computes it once) ->
+ * out_query_feat (B, 128, K) and out_heads: head h is a contiguous (B, head_out[h], K) array at float offset
+ * B * K * (head_out[0] + .. + head_out[h - 1]).  head_out is a HOST array of n_heads entries (0 <= n_heads <= 8, each 1..64);
+ * center_head (or -1) names the head with two outputs that gets query_pos added.  ffn: a multiple of 16 in [16, 1024].
+ *   front  x = query_feat^T; qpe = W2 relu(W1' pos + b1') + b2 (self_posembed, BatchNorm folded); q, k, v = (x + qpe) Win^T + bin
+ *   self   attention(q, k, v) as above with N = K
+ *   mid    x1 = LN1(x + (attn Wo^T + bo)); qc = (x1 + qpe) Wq^T + bq
+ *   kv     K = (lidar_feat^T + key_pe^T) Wk^T + bk, V alike with Wv, bv (the feature map is read channel-major as it is)
+ *   cross  attention(qc, K, V), then the merge
+ *   tail   x2 = LN2(x1 + (attn Wo^T + bo)); x3 = LN3(x2 + (W2 relu(W1 x2 + b1) + b2)) -> out_query_feat;
+ *          head h: W2h relu(W1h' x3 + b1h') + b2h (BatchNorm folded), center += query_pos
+ * LayerNorm: mean, then the biased variance of the centred values, (x - mean) * (1 / sqrt(var + eps)) * gamma + beta, in f32.
+ * Sums over input channels run in ascending channel order per output element.
+ * params: one block of params_floats f32, in this order (row-major, sizes in floats):
+ *   eps of norm1, norm2, norm3, 0 (4) | self_posembed W1' (128 x 2), b1' (128), W2 (128 x 128), b2 (128) |
+ *   self_attn in_proj_weight (384 x 128), in_proj_bias (384), out_proj.weight (128 x 128), out_proj.bias (128) |
+ *   norm1 weight, bias (128, 128) | multihead_attn in_proj_weight, in_proj_bias, out_proj.weight, out_proj.bias (as self_attn) |
+ *   norm2 weight, bias | linear1.weight (ffn x 128), bias (ffn), linear2.weight (128 x ffn), bias (128) | norm3 weight, bias |
+ *   heads' first convolutions stacked (64 n_heads x 128) and biases (64 n_heads), BatchNorm folded: W' = W * s,
+ *   b' = (b - running_mean) * s + beta, s = gamma / sqrt(running_var + eps) |
+ *   heads' last convolutions, head h padded with zero rows to 16 * ceil(head_out[h] / 16) rows of 64, then the biases padded alike.
+ * Out of contract: training mode (dropout, batch statistics), masks, d_model != 128, nhead != 8, non-finite inputs.
+ * workspace: fnp_tf_decoder_workspace_bytes(B, K, N, ffn, n_head_out = the sum of head_out) bytes.
+ *
+ * fnp_tf_decoder_stages: fnp_tf_decoder's arguments and a mask of the stages to launch (bit 0 front, 1 self-attention, 2 mid,
+ * 3 kv_proj, 4 cross-attention with its merge, 5 tail; 63 is fnp_tf_decoder).  A stage reads what the stages in front of it left in
+ * the workspace: on the workspace of a complete call any single stage can be launched again, which is how tools/bench_decoder.py
+ * times each kernel on its own.  (After a complete call the attention output buffer holds the cross attention's rows, so `mid`
+ * run alone is good for its time, not for its values.) */
+int fnp_tf_attention_geometry(int64_t n_keys, int *split_len, int *tile_len);
+int64_t fnp_tf_attention_workspace_bytes(int batch_size, int num_queries, int64_t num_keys);
+int fnp_tf_attention(const float *q, const float *k, const float *v, int batch_size, int num_queries, int64_t num_keys,
+                     void *workspace, int64_t workspace_bytes, float *out, fnp_stream_t stream);
+int64_t fnp_tf_decoder_workspace_bytes(int batch_size, int num_queries, int64_t num_keys, int ffn, int n_head_out);
+int fnp_tf_decoder_stages(const float *query_feat, const float *lidar_feat, const float *query_pos, const float *key_pe,
+                          int key_pe_batched, const float *params, int64_t params_floats, int batch_size, int num_queries,
+                          int64_t num_keys, int ffn, int n_heads, const int *head_out, int center_head, void *workspace,
+                          int64_t workspace_bytes, float *out_query_feat, float *out_heads, int stages, fnp_stream_t stream);
+int fnp_tf_decoder(const float *query_feat, const float *lidar_feat, const float *query_pos, const float *key_pe,
+                   int key_pe_batched, const float *params, int64_t params_floats, int batch_size, int num_queries, int64_t num_keys, int ffn,
+                   int n_heads, const int *head_out, int center_head, void *workspace, int64_t workspace_bytes,
+                   float *out_query_feat, float *out_heads, fnp_stream_t stream);
+
 /* Capacity overflow: data-dependent counts (n_voxels, n_out) always hold the TRUE count; every
  * kernel clamps to the capacity it was given, so a count larger than its capacity means rows
  * were dropped and the caller must re-run with larger buffers. */
