@@ -29,6 +29,7 @@
 // gaussian2D's `h[h < eps * h.max()] = 0` is left out: it never fires (the smallest weight of any radius is the corner's,
 // about exp(-9), against eps = 2.2e-16).
 #include "common.h"
+#include "f32io.h"
 
 #include <hip/hip_bf16.h>
 #include <hip/hip_fp16.h>
@@ -172,23 +173,6 @@ __global__ __launch_bounds__(kThreads) void hm_count_kernel(const int *__restric
 }
 
 // ---- loss ----------------------------------------------------------------------------------------------------------
-
-template <typename T> __device__ __forceinline__ float load_f32(const T *p, long long i);
-template <> __device__ __forceinline__ float load_f32<float>(const float *p, long long i) { return p[i]; }
-template <> __device__ __forceinline__ float load_f32<__half>(const __half *p, long long i) { return __half2float(p[i]); }
-template <> __device__ __forceinline__ float load_f32<unsigned short>(const unsigned short *p, long long i) {   // bf16 bits
-    return __uint_as_float((unsigned)p[i] << 16);
-}
-template <typename T> __device__ __forceinline__ void store_f32(T *p, long long i, float v);
-template <> __device__ __forceinline__ void store_f32<float>(float *p, long long i, float v) { p[i] = v; }
-template <> __device__ __forceinline__ void store_f32<__half>(__half *p, long long i, float v) { p[i] = __float2half_rn(v); }
-template <> __device__ __forceinline__ void store_f32<unsigned short>(unsigned short *p, long long i, float v) {
-    const unsigned u = __float_as_uint(v);
-    unsigned short r;
-    if ((u & 0x7fffffffu) > 0x7f800000u) r = (unsigned short)((u >> 16) | 0x40u);          // NaN stays a NaN
-    else r = (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);                     // round to nearest even
-    p[i] = r;
-}
 
 // clip_sigmoid: p = clamp(1 / (1 + exp(-x)), f32(1e-4), f32(1 - 1e-4)); `inside` = the clamp passes the gradient.
 // GaussianFocalLoss adds eps = 1e-12 to p and to 1 - p before the logarithm: both are >= 1e-4, whose f32 spacing is 7e-12, so

@@ -19,121 +19,9 @@
 #include <cmath>
 #include <vector>
 
+#include "boxoverlap.h"
+
 namespace {
-
-struct P2 {
-    float x, y;
-};
-
-struct RBox {           // one rotated rectangle, prepared once
-    float raw[7];
-    P2 c[5];            // rotated corners, c[4] == c[0]
-    float ncos, nsin;   // cos(-heading), sin(-heading) for the corner-inside test
-    float hx, hy;       // dx/2 + 1e-2f, dy/2 + 1e-2f (f32, :61)
-};
-
-__host__ __device__ __forceinline__ float cross3(const P2 &p1, const P2 &p2, const P2 &p0) {
-    return (p1.x - p0.x) * (p2.y - p0.y) - (p2.x - p0.x) * (p1.y - p0.y);
-}
-
-__host__ __device__ __forceinline__ void prep_box(const float *b, RBox &r) {
-#pragma unroll
-    for (int i = 0; i < 7; ++i) r.raw[i] = b[i];
-    const float hx = b[3] / 2, hy = b[4] / 2;
-    const float cx = b[0], cy = b[1];
-    const float cs = cosf(b[6]), sn = sinf(b[6]);
-    const float ox[4] = {cx - hx, cx + hx, cx + hx, cx - hx};
-    const float oy[4] = {cy - hy, cy - hy, cy + hy, cy + hy};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        r.c[k].x = (ox[k] - cx) * cs + (oy[k] - cy) * (-sn) + cx;
-        r.c[k].y = (ox[k] - cx) * sn + (oy[k] - cy) * cs + cy;
-    }
-    r.c[4] = r.c[0];
-    r.ncos = cosf(-b[6]);
-    r.nsin = sinf(-b[6]);
-    r.hx = b[3] / 2 + 1e-2f;
-    r.hy = b[4] / 2 + 1e-2f;
-}
-
-__host__ __device__ __forceinline__ bool corner_inside(const RBox &box, const P2 &p) {
-    const float rx = (p.x - box.raw[0]) * box.ncos + (p.y - box.raw[1]) * (-box.nsin);
-    const float ry = (p.x - box.raw[0]) * box.nsin + (p.y - box.raw[1]) * box.ncos;
-    return fabsf(rx) < box.hx && fabsf(ry) < box.hy;
-}
-
-__host__ __device__ __forceinline__ bool seg_cross(const P2 &p1, const P2 &p0, const P2 &q1, const P2 &q0, P2 &ans) {
-    const bool bb = fminf(p0.x, p1.x) <= fmaxf(q0.x, q1.x) && fminf(q0.x, q1.x) <= fmaxf(p0.x, p1.x) &&
-                    fminf(p0.y, p1.y) <= fmaxf(q0.y, q1.y) && fminf(q0.y, q1.y) <= fmaxf(p0.y, p1.y);
-    if (!bb) return false;
-    const float s1 = cross3(q0, p1, p0);
-    const float s2 = cross3(p1, q1, p0);
-    const float s3 = cross3(p0, q1, q0);
-    const float s4 = cross3(q1, p1, q0);
-    if (!(s1 * s2 > 0 && s3 * s4 > 0)) return false;
-    const float s5 = cross3(q1, p1, p0);
-    if (fabsf(s5 - s1) > 1e-8f) {
-        ans.x = (s5 * q0.x - s1 * q1.x) / (s5 - s1);
-        ans.y = (s5 * q0.y - s1 * q1.y) / (s5 - s1);
-    } else {
-        const float a0 = p0.y - p1.y, b0 = p1.x - p0.x, c0 = p0.x * p1.y - p1.x * p0.y;
-        const float a1 = q0.y - q1.y, b1 = q1.x - q0.x, c1 = q0.x * q1.y - q1.x * q0.y;
-        const float D = a0 * b1 - a1 * b0;
-        ans.x = (b0 * c1 - b1 * c0) / D;
-        ans.y = (a1 * c0 - a0 * c1) / D;
-    }
-    return true;
-}
-
-__host__ __device__ float overlap_area(const RBox &A, const RBox &B) {
-    P2 poly[24];
-    float key[24];
-    int cnt = 0;
-    float sx = 0.f, sy = 0.f;
-    for (int i = 0; i < 4; ++i)
-        for (int j = 0; j < 4; ++j) {
-            P2 x;
-            if (seg_cross(A.c[i + 1], A.c[i], B.c[j + 1], B.c[j], x)) {
-                sx = sx + x.x;
-                sy = sy + x.y;
-                poly[cnt++] = x;
-            }
-        }
-    for (int k = 0; k < 4; ++k) {
-        if (corner_inside(A, B.c[k])) {
-            sx = sx + B.c[k].x;
-            sy = sy + B.c[k].y;
-            poly[cnt++] = B.c[k];
-        }
-        if (corner_inside(B, A.c[k])) {
-            sx = sx + A.c[k].x;
-            sy = sy + A.c[k].y;
-            poly[cnt++] = A.c[k];
-        }
-    }
-    if (cnt < 3) return 0.f;  // fan over < 3 vertices has zero area (reference: empty loop / zero cross)
-    const float mx = sx / cnt, my = sy / cnt;
-    for (int i = 0; i < cnt; ++i) key[i] = atan2f(poly[i].y - my, poly[i].x - mx);
-    for (int i = 1; i < cnt; ++i) {  // stable insertion sort, ascending
-        const P2 p = poly[i];
-        const float k = key[i];
-        int j = i - 1;
-        while (j >= 0 && key[j] > k) {
-            poly[j + 1] = poly[j];
-            key[j + 1] = key[j];
-            --j;
-        }
-        poly[j + 1] = p;
-        key[j + 1] = k;
-    }
-    float area = 0.f;
-    for (int k = 0; k < cnt - 1; ++k) {
-        const float ux = poly[k].x - poly[0].x, uy = poly[k].y - poly[0].y;
-        const float vx = poly[k + 1].x - poly[0].x, vy = poly[k + 1].y - poly[0].y;
-        area += ux * vy - uy * vx;
-    }
-    return fabsf(area) * 0.5f;  // == (float)(fabs(area) / 2.0)
-}
 
 __host__ __device__ __forceinline__ float iou_from_overlap(const float *a, const float *b, float ov) {
     const float sa = a[3] * a[4], sb = b[3] * b[4];
@@ -525,6 +413,18 @@ extern "C" int fnp_host_boxes_iou_bev(const float *a, int na, const float *b, in
         prep_box(a + (size_t)i * 7, A);
         for (int j = 0; j < nb; ++j)
             out[(size_t)i * nb + j] = iou_from_overlap(a + (size_t)i * 7, b + (size_t)j * 7, overlap_area(A, pb[j]));
+    }
+    return FNP_OK;
+}
+
+extern "C" int fnp_host_boxes_overlap_bev(const float *a, int na, const float *b, int nb, float *out) {
+    if (na < 0 || nb < 0 || ((na > 0 && nb > 0) && (!a || !b || !out))) return FNP_ERR_ARG;
+    std::vector<RBox> pb((size_t)nb);
+    for (int j = 0; j < nb; ++j) prep_box(b + (size_t)j * 7, pb[j]);
+    for (int i = 0; i < na; ++i) {
+        RBox A;
+        prep_box(a + (size_t)i * 7, A);
+        for (int j = 0; j < nb; ++j) out[(size_t)i * nb + j] = overlap_area(A, pb[j]);
     }
     return FNP_OK;
 }

@@ -34,6 +34,7 @@
 // MASKED VALUE: prop_prob() and prop_masked() below are the only definition of it; the selecting pass and the
 // query_heatmap_score pass both call them, so the two cannot disagree.
 #include "common.h"
+#include "tfdecode.h"
 
 namespace {
 
@@ -360,13 +361,8 @@ __global__ __launch_bounds__(kThreads) void tf_decode_kernel(const float *__rest
             }
             label = v > 0.f ? (int)q : 0;      // the maximum over an all-zero column is at index 0
             score = v > 0.f ? v : 0.f;
-            box[0] = center[((size_t)b * 2 + 0) * K + k] * cfg.stride * cfg.vx + cfg.x0;
-            box[1] = center[((size_t)b * 2 + 1) * K + k] * cfg.stride * cfg.vy + cfg.y0;
-            box[2] = height[(size_t)b * K + k];
-            for (int j = 0; j < 3; ++j) box[3 + j] = (float)exp((double)dim[((size_t)b * 3 + j) * K + k]);
-            box[6] = (float)atan2((double)rot[((size_t)b * 2 + 0) * K + k], (double)rot[((size_t)b * 2 + 1) * K + k]);
-            box[7] = box[8] = 0.f;
-            if (cfg.has_vel) box[7] = vel[((size_t)b * 2 + 0) * K + k], box[8] = vel[((size_t)b * 2 + 1) * K + k];
+            tf_decode_box(center, height, dim, rot, cfg.has_vel ? vel : nullptr, (size_t)b, k, K, cfg.stride, cfg.vx, cfg.vy, cfg.x0,
+                          cfg.y0, box);
             const float thresh = ((cfg.unk_mask >> label) & 1ull) ? cfg.thresh_unk : cfg.thresh;   // bit (1-based label - 1)
             keep = score > thresh;
             for (int j = 0; j < 3; ++j) keep = keep && box[j] >= cfg.rmin[j] && box[j] <= cfg.rmax[j];

@@ -216,6 +216,18 @@ SIGNATURES = {
                                P, P, P]),
     "fnp_tf_decoder_stages": (c_int, [P, P, P, P, c_int, P, c_int64, c_int, c_int, c_int64, c_int, c_int, POINTER(c_int), c_int, P,
                                       c_int64, P, P, c_int, P]),
+    "fnp_host_boxes_overlap_bev": (c_int, [P, c_int, P, c_int, P]),
+    "fnp_host_lsap": (c_int, [P, c_int, c_int, P, P]),
+    "fnp_tf_assign_match": (c_int, [P, P, P, P, c_int, c_int, c_int, P, P, P]),
+    "fnp_tf_assign_cost": (c_int, [P, P, P, P, P, P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_float, c_float, POINTER(c_float),
+                                   c_double, c_double, c_double, c_double, c_double, c_double, P, P, P, P, P, P]),
+    "fnp_tf_query_loss_workspace_bytes": (c_int64, []),
+    "fnp_tf_query_loss_forward": (c_int, [P, POINTER(c_void_p), POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P,
+                                          c_double, c_double, POINTER(c_float), POINTER(c_float), c_double, P, c_int64, P, P]),
+    "fnp_tf_query_loss_backward": (c_int, [P, POINTER(c_void_p), POINTER(c_int), c_int, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P,
+                                           c_double, c_double, POINTER(c_float), POINTER(c_float), c_double, P, P, POINTER(c_void_p), P]),
+    "fnp_tf_assign_targets": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_float, c_float, c_uint64,
+                                      P, P, P, P, P, P, P]),
 }
 
 

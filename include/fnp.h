@@ -122,6 +122,9 @@ int fnp_host_points_in_boxes_compact(const float *points, int64_t n, int C, cons
  * pseudo-label mixing in dataloader workers (pseudo_loader.py:29-55).  Host pointers, (n,7) boxes. */
 int fnp_host_boxes_iou_bev(const float *boxes_a, int na, const float *boxes_b, int nb, float *iou_out);
 int fnp_host_boxes_aligned_iou_bev(const float *boxes_a, const float *boxes_b, int n, float *iou_out);
+/* The host twin of fnp_boxes_overlap_bev: overlap_out (na, nb) f32 = the BEV overlap AREA, the same function as the IoU above
+ * before its division (additive, ABI 14).  The golden generator of the target assignment feeds it to the reference. */
+int fnp_host_boxes_overlap_bev(const float *boxes_a, int na, const float *boxes_b, int nb, float *overlap_out);
 
 /* Bytes of the u64 suppression-mask workspace for N boxes. */
 int64_t fnp_nms_workspace_bytes(int num_boxes);
@@ -964,6 +967,97 @@ int fnp_tf_decoder(const float *query_feat, const float *lidar_feat, const float
                    int key_pe_batched, const float *params, int64_t params_floats, int batch_size, int num_queries, int64_t num_keys, int ffn,
                    int n_heads, const int *head_out, int center_head, void *workspace, int64_t workspace_bytes,
                    float *out_query_feat, float *out_heads, fnp_stream_t stream);
+
+/* Hungarian assignment and per-query targets of TransFusionHead (transfusion_head.py:352-444, hungarian_assigner.py:61-132;
+ * additive, ABI 14; csrc/tfassign.hip).  The batch goes in four launches (valid rows, cost, match, targets); every device call
+ * takes a stream, allocates nothing, calls no synchronising HIP function and uses no atomics: results are bit-identical from
+ * run to run, and a scene's results are the same alone or in a batch.  Parity is with the reference run on the CPU.
+ *
+ * fnp_tf_assign_cost: the head outputs heatmap (logits, B, C, K), center (B, 2, K), height (B, 1, K), dim (B, 3, K), rot
+ * (B, 2, K: sin, cos), vel (B, 2, K; required when ncol == 10, else ignored), all f32, and gt_boxes (B, Mcap, ncol) f32,
+ * ncol = 10 (x y z dx dy dz yaw vx vy label) or 8 (no velocities), label 1-based, 0 = padding.
+ *   1. Valid rows: dx > 0 and dy > 0 (the reference's "filter empty boxes"), a label inside 1..num_classes (a fraction is
+ *      truncated, as the reference's .long() does) and finite x, y, dx, dy.  The reference wraps on a label below 1 and raises on one above num_classes; both are out of contract here and
+ *      skipped, the rule of fnp_heatmap_box_params.  num_valid (B) int32 = their number; valid_map (B, Mcap) int32 = their row
+ *      indices in ascending order, -1 behind them.
+ *   2. Decode (decode_bbox, filter = False): the sequence of fnp_tf_decode (one device function, csrc/tfdecode.h): centres bit
+ *      for bit, exp(dim) and atan2 in f64 rounded once.  boxes (B, K, 9 or 7) or NULL receives the decoded rows.
+ *   3. cost[b, k, j] for j < num_valid[b], the box being row valid_map[b, j]: cls + reg + iou_cost, f32, in that order.
+ *      cls = (pos - neg) * cls_weight with p = sigmoid(heatmap[b, label - 1, k]), neg = -log(1 - p + eps) * (1 - alpha) * p^gamma,
+ *      pos = -log(p + eps) * alpha * (1 - p)^gamma (f32 expf / logf; p^2 is a product);  reg = (|dx| + |dy|) * reg_weight of the
+ *      centres normalised as (v - range[0:2]) / (range[3:5] - range[0:2]);  iou_cost = -iou * iou_weight.
+ *   4. iou[b, k, j] = the reference's overlaps(): BEV overlap (the function behind fnp_boxes_overlap_bev, csrc/boxoverlap.h)
+ *      times the height overlap with z as the BOTTOM of a box, over clamp(vol_q + vol_g - overlap, 1e-8); plain IEEE f32 in the
+ *      reference's operand order.  Columns j >= num_valid[b] of cost and iou are 0: every element is written.
+ * point_cloud_range: a HOST array of 6 floats.  Python scalars (weights, alpha, 1 - alpha, eps) meet the tensors as their f32
+ * roundings.  Every argument is checked before the first launch: a call that returns an error has written nothing.  B <= 65535, C <= 64, K <= 2048, Mcap <= 1024.  Two launches.
+ *
+ * fnp_tf_assign_targets (transfusion_head.py:401-444): assigned (B, K) int32 as fnp_tf_assign_match writes it (original row
+ * of gt_boxes or -1) -> labels (B, K) int64: the box's label - 1 at a match, num_classes elsewhere; label_weights (B, K) f32:
+ * 1 everywhere (the reference's outcome for positives and negatives alike); bbox_targets (B, K, ncol) f32: encode_bbox at a
+ * match ((x - range_x) / f32(stride * voxel_x), y alike, z, log of the sizes, sin and cos of the yaw, the velocities when
+ * ncol == 10; the divisions, log, sin and cos formed in f64 and rounded once), 0 elsewhere; bbox_weights (B, K, ncol): 1 at a
+ * match, else 0; unknown (B, K) bytes 0 / 1: the matched label has its bit (label - 1) set in unknown_mask; num_pos (1) int32:
+ * the number of matches of the batch, an integer sum.  One launch.
+ *
+ * The matching: both functions below reproduce scipy.optimize.linear_sum_assignment (scipy >= 1.4, the
+ * shortest-augmenting-path solver) exactly, ties included: the matrix is transposed when it has fewer columns than rows, the
+ * reduced costs are formed in f64 on the f32 costs widened, in scipy's operand order, and scipy's scan order and tie rule
+ * are kept (csrc/lsap.h states them).  Costs must be finite; with a NaN or an infinity the result is unspecified, but every
+ * loop is bounded: each inner step removes a column.
+ *
+ * fnp_host_lsap: HOST arrays, serial.  cost (nr, nc) f32 row-major -> rows, cols (min(nr, nc)) int32, rows ascending, as
+ * scipy returns them.  FNP_ERR_ARG when no finite assignment exists.
+ *
+ * fnp_tf_assign_match: cost (B, K, Mcap) f32 on the device, of which scene b uses the K x num_valid[b] leading columns
+ * (num_valid (B) int32 on the device, clamped to 0..Mcap; the columns are the scene's valid boxes, compacted in ascending row
+ * order) -> assigned (B, K) int32: per query the matched box, or -1.  The box is named by valid_map[b, column] (valid_map
+ * (B, Mcap) int32, compact column -> original row of gt_boxes) or, with valid_map NULL, by the column itself.  matched_iou
+ * (B, K) f32 or NULL: iou[b, k, column] (iou (B, K, Mcap) f32) at the match, clamped to [0, 1], else 0.  A scene with
+ * num_valid 0 gets no match.  K <= 2048, Mcap <= 1024.  One launch for the batch, one wave per scene; takes a stream,
+ * allocates nothing, calls no synchronising HIP function and uses no atomics: results are bit-identical from run to run,
+ * and a scene's result is the same alone or in a batch. */
+int fnp_host_lsap(const float *cost, int nr, int nc, int *rows, int *cols);
+int fnp_tf_assign_match(const float *cost, const float *iou, const int *num_valid, const int *valid_map, int batch_size,
+                        int num_queries, int max_boxes, int *assigned, float *matched_iou, fnp_stream_t stream);
+int fnp_tf_assign_cost(const float *heatmap, const float *center, const float *height, const float *dim, const float *rot,
+                       const float *vel, const float *gt_boxes, int batch_size, int num_classes, int num_queries, int max_boxes,
+                       int ncol, int feature_map_stride, float voxel_x, float voxel_y, const float *point_cloud_range,
+                       double cls_weight, double alpha, double gamma, double eps, double reg_weight, double iou_weight,
+                       int *num_valid, int *valid_map, float *cost, float *iou, float *boxes, fnp_stream_t stream);
+int fnp_tf_assign_targets(const int *assigned, const float *gt_boxes, int batch_size, int num_classes, int num_queries,
+                          int max_boxes, int ncol, int feature_map_stride, double voxel_x, double voxel_y, float range_x,
+                          float range_y, uint64_t unknown_mask, int64_t *labels, float *label_weights, float *bbox_targets,
+                          float *bbox_weights, unsigned char *unknown, int *num_pos, fnp_stream_t stream);
+
+/* The two losses behind the per-query targets (transfusion_head.py:500-504, :561-597, the default configuration:
+ * SigmoidFocalClassificationLoss without label smoothing or balanced reweighting, L1Loss; additive, ABI 14; csrc/tfassign.hip).
+ * heatmap (logits, B, C, K) and the n_heads <= 8 regression heads in HEAD_ORDER, head h (B, head_channels[h], K), all of `dtype`
+ * (FNP_F32, FNP_F16, FNP_BF16; upcast exactly), read where they lie: no cat, no permute.  heads, head_channels, code_weights and
+ * unknown_code_weights (or NULL) are HOST arrays; the channels sum to code_size <= 16.  labels, label_weights, bbox_targets,
+ * bbox_weights, unknown and num_pos as fnp_tf_assign_targets writes them.
+ * forward: loss[0] = sum(focal * bce * w) / max(*num_pos, 1), loss[1] = sum(|pred - target| * rw) / max(*num_pos, 1), with
+ * t = 1 at column labels[b, k]; p = sigmoid(x); focal = (t alpha + (1 - t)(1 - alpha)) * pt^gamma, pt = t (1 - p) + (1 - t) p;
+ * bce = max(x, 0) - x t + log1p(exp(-|x|)); w = label_weights, times unknown_cls_weight where unknown is set (pass 1 when not
+ * configured); rw = bbox_weights * code_weights, times unknown_code_weights where unknown is set.  f32 per element, f64 partial
+ * sums in a fixed order: bit-identical from run to run.  Two launches.  workspace: fnp_tf_query_loss_workspace_bytes(), 8-byte
+ * aligned.
+ * backward: grad_heatmap and grad_heads[h] (`dtype`, the layouts of their inputs) = the derivative, recomputed, times
+ * grad_out[0 or 1] / max(*num_pos, 1) (grad_out: 2 f32 on the device).  The focal weight is differentiated through; the L1
+ * gradient is sign(pred - target), 0 at equality.  One launch.  Neither call allocates or synchronises. */
+int64_t fnp_tf_query_loss_workspace_bytes(void);
+int fnp_tf_query_loss_forward(const void *heatmap, const void *const *heads, const int *head_channels, int n_heads, int dtype,
+                              int batch_size, int num_classes, int num_queries, int code_size, const int64_t *labels,
+                              const float *label_weights, const float *bbox_targets, const float *bbox_weights,
+                              const unsigned char *unknown, const int *num_pos, double alpha, double gamma,
+                              const float *code_weights, const float *unknown_code_weights, double unknown_cls_weight,
+                              void *workspace, int64_t workspace_bytes, float *loss, fnp_stream_t stream);
+int fnp_tf_query_loss_backward(const void *heatmap, const void *const *heads, const int *head_channels, int n_heads, int dtype,
+                               int batch_size, int num_classes, int num_queries, int code_size, const int64_t *labels,
+                               const float *label_weights, const float *bbox_targets, const float *bbox_weights,
+                               const unsigned char *unknown, const int *num_pos, double alpha, double gamma,
+                               const float *code_weights, const float *unknown_code_weights, double unknown_cls_weight,
+                               const float *grad_out, void *grad_heatmap, void *const *grad_heads, fnp_stream_t stream);
 
 /* Capacity overflow: data-dependent counts (n_voxels, n_out) always hold the TRUE count; every
  * kernel clamps to the capacity it was given, so a count larger than its capacity means rows
