@@ -883,6 +883,7 @@ extern "C" int fnp_boxseeker(const float *points, const int *scene_offsets, int 
     const bool opt = params->topk > 1 || params->search_depth > 0.f || params->occl_w > 0.f || params->occl_mult || params->multicam ||
                      params->count_only || params->rand_noise;
     // small launches (fewer workgroups than two per CU): the instantiation built for a frustum's latency
+    // (tests/seeker_parity.py restates the bound as SEEKER_LAT_MAX_FRUSTUMS to launch on both sides of it: the two move together)
     const bool lat = num_frustums <= 512;
 #define FNP_BS_LAUNCH(O, L)                                                                                                     \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(boxseeker_kernel<O, L>), dim3(num_frustums), dim3(kThreads), 0, (hipStream_t)stream, points,            \

@@ -378,7 +378,9 @@ class FrustumProposerOG(nn.Module):
         if debug:
             # the lidar-frame points of every frustum as the kernel counted them (second half of its workspace: (F, stride, 3) f32,
             # the first npts[f] rows of frustum f) — what the reference hands to points_in_boxes_gpu per candidate (:812-815,930-932)
+            # — and, in the first half, the same rows as the kernel selected them: [u, v, depth] in the frustum's camera (:606-613)
             stride = max(max_pts, 1)
+            dbg['points_uvd'] = ws[: F * stride * 12].view(torch.float32).view(F, stride, 3)
             dbg['points_xyz'] = ws[F * stride * 12: 2 * F * stride * 12].view(torch.float32).view(F, stride, 3)
         out_count = out_valid
         if TK > 1:   # row form (device ops, no sync): one row per (frustum, rank), valid while rank < the frustum's box count
