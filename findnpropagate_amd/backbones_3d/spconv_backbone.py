@@ -904,7 +904,7 @@ class FusedResBackbone:
         (whi, wlo, ones), _, shift = prm
         res = None if residual is None else residual[2]
         C = int(whi.shape[1])
-        fast = ranked and (C in getattr(rb, "_tile_rb", {}) or (C == 128 and getattr(rb, "_sorted", None) is not None))
+        fast = ranked and (C in (rb._tile_rb or ()) or (C == 128 and rb._sorted is not None))
         # the two cross terms are 2^-8 of the result: bf16 precision is enough for them, so they run with bf16 outputs (on the
         # bf16 engine's tile-rulebook / class-sorted kernels where the stage has them) chained through a bf16 residual; only the
         # main product keeps f32, and ITS epilogue adds them, applies the ReLU and writes the f32 rows with their (hi, lo) split
@@ -1065,7 +1065,7 @@ class FusedResBackbone:
             tag = (int(w.shape[2]), int(w.shape[1]), int(w.shape[0]), residual is not None, ranked)  # Cin, Cout, K, res
             if self.rulebook_log is not None:
                 self.rulebook_log.append((tag, rb, n))
-            if getattr(rb, "_ell", None) is not None and (rb.nbr is None or int(w.shape[2]) <= 8):   # on the compact rulebook
+            if rb._ell is not None and (rb.nbr is None or int(w.shape[2]) <= 8):   # on the compact rulebook
                 fn, args, kw = S.conv_forward_ell, (x, w, rb, n), dict(out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True)
             elif rb.nbr is None:   # fused strided layer
                 fn, args, kw = S.conv_forward_strided, (x, w, rb), dict(scale=sc, shift=sh, relu=True)

@@ -13,7 +13,7 @@ Data layout in HBM:
 """
 import ctypes
 import os
-from dataclasses import dataclass
+from dataclasses import dataclass, field
 from typing import List, Optional
 
 import torch
@@ -54,7 +54,7 @@ class RankGrid:
             self.counters.zero_()
 
 
-@dataclass
+@dataclass(slots=True)
 class Rulebook:
     nbr: torch.Tensor             # (K, cap_out) int32
     K: int
@@ -65,6 +65,30 @@ class Rulebook:
     out_grid: Optional[RankGrid] = None
     out_shape: Optional[List[int]] = None
     in_grid: Optional[RankGrid] = None           # strided, nbr is None: the grid the convolution looks its inputs up in
+    # DERIVED STATE: None until its writer has run, then valid as long as nbr and the row count are (a Rulebook is never rewritten
+    # in place).  The class has slots: these are all there are, and a misspelt name raises instead of choosing another kernel.
+    # {channels: tile rulebook}; rulebook_subm(tile_channels=) and tile_rulebook write it, forward_route's tiled kernels read it
+    _tile_rb: Optional[dict] = field(default=None, init=False, repr=False)
+    # nbr holds the rows of escape tiles only; rulebook_subm(lean_table=True) writes it, forward_route, tile_rulebook and conv_wgrad refuse it
+    _lean: Optional[bool] = field(default=None, init=False, repr=False)
+    # the next strided layer's sites are marked; rulebook_subm(mark_next=) writes it, its caller reads it for rulebook_strided(premarked=)
+    _marked_next: Optional[bool] = field(default=None, init=False, repr=False)
+    # (cap,) int32 neighbour masks; rulebook_subm(masks=True) or classsort writes it, classsort and classsort_f32 read it
+    _rowmask: Optional[torch.Tensor] = field(default=None, init=False, repr=False)
+    # (perm, blockmask); classsort writes it, forward_route's class-sorted sweep, the backward's choice and the engine read it
+    _sorted: Optional[tuple] = field(default=None, init=False, repr=False)
+    # {channels: perm}; classsort_f32 writes it, forward_route's f32 sorted sweep reads it
+    _perm_f32: Optional[dict] = field(default=None, init=False, repr=False)
+    # (records, pool_records, pool_used); rulebook_subm_ell and ell_for_strided write it, conv_forward_ell and the engine read it
+    _ell: Optional[tuple] = field(default=None, init=False, repr=False)
+    # the fused engine's tile gate writes it on the rulebooks of one forward; forward_route then takes a tiled kernel only when told to
+    _no_tile: Optional[bool] = field(default=None, init=False, repr=False)
+    # (pair_o, pair_i, pair_count); rulebook_pairs writes it, conv_wgrad reads it for every layer and backward on this rulebook
+    _pairs: Optional[tuple] = field(default=None, init=False, repr=False)
+    # (K, cap_in) int32; transposed_table writes it and remakes it when the input's row count differs, conv_dgrad's callers read it
+    _nbr_t: Optional[torch.Tensor] = field(default=None, init=False, repr=False)
+    # (indices, shape, n_dev, rank grid) of a strided layer's input; SparseConvolution.forward writes it, SparseInverseConv3d reads it
+    _in_side: Optional[tuple] = field(default=None, init=False, repr=False)
 
 
 # counted marks (round 6, fnp.h fnp_rankgrid.counters): the marking kernels count the cells they set and the rank prefix is one
@@ -514,6 +538,7 @@ def rulebook_subm(indices, n_dev, grid, ksize, tile_channels=None, masks=False, 
     geom, _ = make_geom(ksize, 1, [k // 2 for k in _triple(ksize)], grid.shape, grid.shape)
     K = geom.ksize[0] * geom.ksize[1] * geom.ksize[2]
     nbr = torch.empty((K, cap), dtype=torch.int32, device=indices.device)
+    rb = Rulebook(nbr=nbr, K=K, cap_out=cap, geom=geom)
     mg, mgeom = None, None
     if mark_next is not None:
         out_grid, mk, ms, mp = mark_next
@@ -530,7 +555,6 @@ def rulebook_subm(indices, n_dev, grid, ksize, tile_channels=None, masks=False, 
         else:
             rc = L.fnp_rulebook_subm_tiled(_l.ptr(indices), _l.ptr(n_dev), cap, geom, grid.c(), _l.ptr(nbr), tile_channels, _l.ptr(t), _l.stream())
         _l.check(rc, "fnp_rulebook_subm_tiled")
-        rb = Rulebook(nbr=nbr, K=K, cap_out=cap, geom=geom)
         rb._tile_rb = {tile_channels: t}
         rb._lean = bool(lean_table)
         rb._marked_next = bool(lean_table and mg is not None)
@@ -539,13 +563,12 @@ def rulebook_subm(indices, n_dev, grid, ksize, tile_channels=None, masks=False, 
         rowmask = torch.empty((cap,), dtype=torch.int32, device=indices.device)
         rc = L.fnp_rulebook_subm_masked(_l.ptr(indices), _l.ptr(n_dev), cap, geom, grid.c(), _l.ptr(nbr), _l.ptr(rowmask), mg, mgeom, _l.stream())
         _l.check(rc, "fnp_rulebook_subm_masked")
-        rb = Rulebook(nbr=nbr, K=K, cap_out=cap, geom=geom)
         rb._rowmask = rowmask
         rb._marked_next = mg is not None
         return rb
     rc = L.fnp_rulebook_subm(_l.ptr(indices), _l.ptr(n_dev), cap, geom, grid.c(), _l.ptr(nbr), _l.stream())
     _l.check(rc, "fnp_rulebook_subm")
-    return Rulebook(nbr=nbr, K=K, cap_out=cap, geom=geom)
+    return rb
 
 
 def tiled_by_default(channels, dtype, cap):
@@ -661,28 +684,34 @@ TILE_MODE = {"0": False, "1": True}.get(os.environ.get("FNP_TILE", ""))
 def tile_rulebook(rb, n_out_dev, channels):
     """The tile rulebook of a 3x3x3 rulebook for `channels`-channel layers (fnp_tile_rulebook_build),
     built on first use and kept with it: valid as long as rb.nbr and the row count are (a Rulebook object is never rewritten in place)."""
-    cache = rb.__dict__.setdefault("_tile_rb", {})
-    key = channels
-    t = cache.get(key)
+    if rb._tile_rb is None:
+        rb._tile_rb = {}
+    t = rb._tile_rb.get(channels)
     if t is None:
         L = _l.load()
-        if getattr(rb, "_lean", False):
+        if rb._lean:
             raise _l.FnpError("this rulebook's int32 table holds the rows of escape tiles only: no other tile rulebook can be made from it")
         t = torch.empty((L.fnp_tile_rulebook_bytes(rb.cap_out, channels),), dtype=torch.uint8, device=rb.nbr.device)
         rc = L.fnp_tile_rulebook_build(_l.ptr(rb.nbr), rb.nbr.shape[1], rb.K, _l.ptr(n_out_dev), rb.cap_out, channels, _l.ptr(t), _l.stream())
         _l.check(rc, "fnp_tile_rulebook_build")
-        cache[key] = t
+        rb._tile_rb[channels] = t
     return t
 
 
 TILED_CHANNELS = (32, 64)   # channel counts fnp_spconv_forward_tiled covers
 
 
+def offsets_fit(nbytes):
+    """Can a kernel that addresses a buffer with signed 32-bit byte offsets (fnp.h: the tiled, sorted and f32 MFMA kernels)
+    take one of `nbytes`?  Where not, forward_route falls back to the plain kernel, whose offsets are 64-bit."""
+    return nbytes < 0x7fffffff
+
+
 def tiled_fits(n_in_rows, channels, nbr_stride, cap_out):
     """fnp_spconv_forward_tiled's documented size limit (fnp.h): the feature tensor, the int32 table and the tile rulebook are
     addressed with 32-bit byte offsets."""
     rb_bytes = int(_l.load().fnp_tile_rulebook_bytes(cap_out, channels))
-    return n_in_rows * channels * 2 < 0x7fffffff and 27 * nbr_stride * 4 < 0x7fffffff and rb_bytes < 0x7fffffff
+    return offsets_fit(n_in_rows * channels * 2) and offsets_fit(27 * nbr_stride * 4) and offsets_fit(rb_bytes)
 
 # ... and the ones that take it by themselves (measured at 64 scenes, per layer: 32 channels 0.305 -> 0.18 ms; 64 channels
 # 0.43 -> 0.385 ms, +1 % end to end)
@@ -773,7 +802,7 @@ def classsort(rb, n_out_dev, channels=128):
     dev = rb.nbr.device
     perm = torch.empty((rb.cap_out,), dtype=torch.int32, device=dev)
     blockmask = torch.empty((rb.cap_out // 16 + 1,), dtype=torch.int32, device=dev)
-    rowmask = getattr(rb, "_rowmask", None)
+    rowmask = rb._rowmask
     ws = None
     if rowmask is None:
         ws = torch.empty((int(L.fnp_classsort_workspace_bytes(rb.cap_out)),), dtype=torch.uint8, device=dev)
@@ -800,14 +829,46 @@ def classsort_f32(rb, n_out_dev, channels):
     """Processing order of a 3x3x3 SubM rulebook for the f32 `channels` -> `channels` layers (fnp_rulebook_classsort_f32), kept
     with the rulebook (`rb._perm_f32[channels]`); needs the row masks of rulebook_subm(masks=True).  No host sync."""
     L = _l.load()
-    assert rb.K == 27 and getattr(rb, "_rowmask", None) is not None
+    assert rb.K == 27 and rb._rowmask is not None
     perm = torch.empty((rb.cap_out,), dtype=torch.int32, device=rb.nbr.device)
     rc = L.fnp_rulebook_classsort_f32(_l.ptr(rb._rowmask), _l.ptr(n_out_dev), rb.cap_out, channels, channels, _l.ptr(perm), _l.stream())
     _l.check(rc, "fnp_rulebook_classsort_f32")
-    if getattr(rb, "_perm_f32", None) is None:
+    if rb._perm_f32 is None:
         rb._perm_f32 = {}
     rb._perm_f32[channels] = perm
     return rb
+
+
+ROUTE_TILED, ROUTE_SORTED, ROUTE_F32_SORTED, ROUTE_PLAIN = "tiled", "sorted", "f32_sorted", "plain"
+
+
+def forward_route(rb, K, Cin, Cout, in_dtype, out_dtype, n_in_rows, ranked=False, tile=None, valu=False, split=False):
+    """Which kernel a forward convolution on `rb` runs: one of the ROUTE_ constants, for conv_forward and (split=True, out_dtype
+    unused: it writes f32 and the 16-bit split at once) conv_forward_split.  Every route gives the plain kernel's bits; this is
+    the one place that chooses.  Reads the rulebook's derived state; allocates nothing, launches nothing, never synchronises.
+    Raises on a lean rulebook (rulebook_subm(lean_table=True)) that the tiled kernel does not take.
+    tile: True / False forces / forbids the tile-rulebook kernel; None: TILE_MODE, then the engine's gate (rb._no_tile), then
+    ranked rows of a shape tiled_by_default names.  A tensor beyond a kernel's 32-bit offsets takes the next route: decided
+    HERE from the documented condition, so that any error code of a launch is an error and not a silent change of kernel."""
+    if tile is None:
+        tile = False if (TILE_MODE is None and rb._no_tile) else TILE_MODE
+    half = in_dtype in (torch.bfloat16, torch.float16)
+    same = split or out_dtype == in_dtype     # (the split form has no output dtype to match)
+    if (K == 27 and Cin == Cout and Cin in TILED_CHANNELS and half and same
+            and (tile or (tile is None and ranked and tiled_by_default(Cin, in_dtype, rb.cap_out)))
+            and tiled_fits(n_in_rows, Cin, rb.nbr.shape[1], rb.cap_out)):
+        return ROUTE_TILED
+    if rb._lean:
+        raise _l.FnpError("this rulebook's int32 table holds the rows of escape tiles only (rulebook_subm(lean_table=True)): "
+                          "only the tiled convolution of its channel count may run on it")
+    # (the class-sorted sweep: conv_forward takes it on any rows, the split form on ranked rows only)
+    if (rb._sorted is not None and (ranked or not split) and K == 27 and (Cin, Cout) in SORTED_SHAPES and half and same
+            and offsets_fit(n_in_rows * Cin * 2)):
+        return ROUTE_SORTED
+    if (not split and rb._perm_f32 is not None and rb._perm_f32.get(Cin) is not None and K == 27 and Cin == Cout
+            and in_dtype == torch.float32 and out_dtype == torch.float32 and not valu and offsets_fit(n_in_rows * Cin * 4)):
+        return ROUTE_F32_SORTED
+    return ROUTE_PLAIN
 
 
 def conv_forward(feat_in, w_packed, rb, n_out_dev, out_dtype=None, scale=None, shift=None, residual=None, relu=False,
@@ -819,10 +880,6 @@ def conv_forward(feat_in, w_packed, rb, n_out_dev, out_dtype=None, scale=None, s
     (None: ranked tensors take it; same bits either way)."""
     L = _l.load()
     _l.require_device(feat_in, w_packed, rb.nbr, n_out_dev)
-    if tile is None:
-        tile = TILE_MODE
-    if tile is None and getattr(rb, "_no_tile", False):   # (the fused engine's tile gate: this rulebook's stage runs on the gather kernels)
-        tile = False
     K, Cout, Cin = w_packed.shape
     assert K == rb.K and feat_in.shape[1] == Cin and feat_in.dtype == w_packed.dtype
     assert feat_in.is_contiguous() and w_packed.is_contiguous()
@@ -834,45 +891,26 @@ def conv_forward(feat_in, w_packed, rb, n_out_dev, out_dtype=None, scale=None, s
         assert residual.dtype == out.dtype and residual.shape[1] == Cout and residual.is_contiguous()
     if scale is not None:
         assert scale.dtype == torch.float32 and shift.dtype == torch.float32
-    if (K == 27 and Cin == Cout and Cin in TILED_CHANNELS and feat_in.dtype in (torch.bfloat16, torch.float16) and out.dtype == feat_in.dtype
-            and (tile or (tile is None and ranked and tiled_by_default(Cin, feat_in.dtype, cap_out)))
-            and tiled_fits(feat_in.shape[0], Cin, rb.nbr.shape[1], cap_out)):
-        # (a tensor beyond the tiled kernels' 32-bit offsets takes the gather kernel below: decided HERE from the documented
-        #  condition, so that any error code of the call is an error and not a silent change of kernel)
-        rc = L.fnp_spconv_forward_tiled(_l.ptr(feat_in), _l.dtype_code(feat_in), feat_in.shape[0], _l.ptr(w_packed),
-                                        _l.ptr(tile_rulebook(rb, n_out_dev, Cin)), _l.ptr(rb.nbr), rb.nbr.shape[1], _l.ptr(n_out_dev), cap_out,
-                                        _l.ptr(out), _l.ptr(scale), _l.ptr(shift), _l.ptr(residual), int(bool(relu)), Cin, Cout, _l.stream())
-        _l.check(rc, "fnp_spconv_forward_tiled")
-        return out
-    if getattr(rb, "_lean", False):
-        raise _l.FnpError("this rulebook's int32 table holds the rows of escape tiles only (rulebook_subm(lean_table=True)): "
-                          "only the tiled convolution of its channel count may run on it")
-    srt = getattr(rb, "_sorted", None)
-    if (srt is not None and K == 27 and (Cin, Cout) in SORTED_SHAPES and feat_in.dtype in (torch.bfloat16, torch.float16)
-            and out.dtype == feat_in.dtype and feat_in.shape[0] * Cin * 2 < 0x7fffffff):
-        rc = L.fnp_spconv_forward_sorted(_l.ptr(feat_in), _l.dtype_code(feat_in), feat_in.shape[0], _l.ptr(w_packed), _l.ptr(rb.nbr),
-                                         rb.nbr.shape[1], _l.ptr(srt[0]), _l.ptr(srt[1]), _l.ptr(n_out_dev), cap_out, _l.ptr(out),
-                                         _l.ptr(scale), _l.ptr(shift), _l.ptr(residual), int(bool(relu)), Cin, Cout, _l.stream())
-        _l.check(rc, "fnp_spconv_forward_sorted")
-        return out
-    pf = (getattr(rb, "_perm_f32", None) or {}).get(Cin)
-    if (pf is not None and K == 27 and Cin == Cout and feat_in.dtype == torch.float32 and out.dtype == torch.float32 and not valu
-            and feat_in.shape[0] * Cin * 4 < 0x7fffffff):
-        rc = L.fnp_spconv_forward_f32_sorted(_l.ptr(feat_in), feat_in.shape[0], _l.ptr(w_packed), _l.ptr(rb.nbr), rb.nbr.shape[1], _l.ptr(pf),
-                                             _l.ptr(n_out_dev), cap_out, _l.ptr(out), _l.ptr(scale), _l.ptr(shift), _l.ptr(residual),
-                                             int(bool(relu)), int(isinstance(w_packed, PermutedWeight)), Cin, Cout, _l.stream())
-        _l.check(rc, "fnp_spconv_forward_f32_sorted")
-        return out
-    if isinstance(w_packed, PermutedWeight) and feat_in.shape[0] * Cin * 4 >= 0x7fffffff:
-        # the f32 MFMA kernel addresses the features with 32-bit offsets; beyond them the thread-per-element chain runs,
-        # and it reads the plain (K, Cout, Cin) layout: undo the 4 x 4 transposition of the 16-channel groups
-        w_packed = w_packed.as_subclass(torch.Tensor).view(K, Cout, Cin // 16, 4, 4).transpose(3, 4).contiguous().view(K, Cout, Cin)
-    rc = L.fnp_spconv_forward(_l.ptr(feat_in), _l.dtype_code(feat_in), feat_in.shape[0], _l.ptr(w_packed),
-                              _l.ptr(rb.nbr), rb.nbr.shape[1], K, _l.ptr(n_out_dev), cap_out,
-                              _l.ptr(out), _l.dtype_code(out), _l.ptr(scale), _l.ptr(shift), _l.ptr(residual),
-                              int(bool(relu)), (HINT_ROWS_RANKED if ranked else 0) | (HINT_VALU if valu else 0) |
-                              (HINT_W_PERMUTED if isinstance(w_packed, PermutedWeight) else 0), Cin, Cout, _l.stream())
-    _l.check(rc, "fnp_spconv_forward")
+    route = forward_route(rb, K, Cin, Cout, feat_in.dtype, out.dtype, feat_in.shape[0], ranked, tile, valu)
+    # the argument groups the four entry points share (fnp.h); between them, what each kernel takes of its own
+    rows, table = (_l.ptr(feat_in), _l.dtype_code(feat_in), feat_in.shape[0]), (_l.ptr(rb.nbr), rb.nbr.shape[1])
+    dst, epilogue = (_l.ptr(n_out_dev), cap_out, _l.ptr(out)), (_l.ptr(scale), _l.ptr(shift), _l.ptr(residual), int(bool(relu)))
+    tail = (Cin, Cout, _l.stream())
+    if route == ROUTE_TILED:
+        rc = L.fnp_spconv_forward_tiled(*rows, _l.ptr(w_packed), _l.ptr(tile_rulebook(rb, n_out_dev, Cin)), *table, *dst, *epilogue, *tail)
+    elif route == ROUTE_SORTED:
+        rc = L.fnp_spconv_forward_sorted(*rows, _l.ptr(w_packed), *table, _l.ptr(rb._sorted[0]), _l.ptr(rb._sorted[1]), *dst, *epilogue, *tail)
+    elif route == ROUTE_F32_SORTED:
+        rc = L.fnp_spconv_forward_f32_sorted(_l.ptr(feat_in), feat_in.shape[0], _l.ptr(w_packed), *table, _l.ptr(rb._perm_f32[Cin]), *dst, *epilogue,
+                                             int(isinstance(w_packed, PermutedWeight)), *tail)
+    else:
+        if isinstance(w_packed, PermutedWeight) and not offsets_fit(feat_in.shape[0] * Cin * 4):
+            # the f32 MFMA kernel addresses the features with 32-bit offsets; beyond them the thread-per-element chain runs,
+            # and it reads the plain (K, Cout, Cin) layout: undo the 4 x 4 transposition of the 16-channel groups
+            w_packed = w_packed.as_subclass(torch.Tensor).view(K, Cout, Cin // 16, 4, 4).transpose(3, 4).contiguous().view(K, Cout, Cin)
+        hints = (HINT_ROWS_RANKED if ranked else 0) | (HINT_VALU if valu else 0) | (HINT_W_PERMUTED if isinstance(w_packed, PermutedWeight) else 0)
+        rc = L.fnp_spconv_forward(*rows, _l.ptr(w_packed), *table, K, *dst, _l.dtype_code(out), *epilogue, hints, *tail)
+    _l.check(rc, "fnp_spconv_forward" if route == ROUTE_PLAIN else "fnp_spconv_forward_" + route)
     return out
 
 
@@ -902,32 +940,17 @@ def conv_forward_split(feat_in, w_packed, rb, n_out_dev, scale=None, shift=None,
         assert addend.dtype == feat_in.dtype and addend.shape == hi.shape and addend.is_contiguous()
     if scale is not None:
         assert scale.dtype == torch.float32 and shift.dtype == torch.float32
-    if tile is None:
-        tile = TILE_MODE
-    if tile is None and getattr(rb, "_no_tile", False):
-        tile = False
-    if (K == 27 and Cin == Cout and Cin in TILED_CHANNELS and (tile or (tile is None and ranked and tiled_by_default(Cin, feat_in.dtype, cap_out)))
-            and tiled_fits(feat_in.shape[0], Cin, rb.nbr.shape[1], cap_out)):
-        rc = L.fnp_spconv_forward_tiled_split(_l.ptr(feat_in), _l.dtype_code(feat_in), feat_in.shape[0], _l.ptr(w_packed),
-                                              _l.ptr(tile_rulebook(rb, n_out_dev, Cin)), _l.ptr(rb.nbr), rb.nbr.shape[1], _l.ptr(n_out_dev), cap_out,
-                                              _l.ptr(y), _l.ptr(scale), _l.ptr(shift), _l.ptr(residual), _l.ptr(addend), int(bool(relu)), Cin, Cout,
-                                              _l.ptr(hi), _l.ptr(lo), _l.stream())
-        _l.check(rc, "fnp_spconv_forward_tiled_split")
-        return y, hi, lo
-    if getattr(rb, "_lean", False):
-        raise _l.FnpError("this rulebook's int32 table holds the rows of escape tiles only (rulebook_subm(lean_table=True)): "
-                          "only the tiled convolution of its channel count may run on it")
-    srt = getattr(rb, "_sorted", None)
-    if srt is not None and ranked and K == 27 and (Cin, Cout) in SORTED_SHAPES and feat_in.shape[0] * Cin * 2 < 0x7fffffff:
-        rc = L.fnp_spconv_forward_sorted_split(_l.ptr(feat_in), _l.dtype_code(feat_in), feat_in.shape[0], _l.ptr(w_packed), _l.ptr(rb.nbr), rb.nbr.shape[1],
-                                               _l.ptr(srt[0]), _l.ptr(srt[1]), _l.ptr(n_out_dev), cap_out, _l.ptr(y), _l.ptr(scale), _l.ptr(shift),
-                                               _l.ptr(residual), _l.ptr(addend), int(bool(relu)), Cin, Cout, _l.ptr(hi), _l.ptr(lo), _l.stream())
-        _l.check(rc, "fnp_spconv_forward_sorted_split")
-        return y, hi, lo
-    rc = L.fnp_spconv_forward_split(_l.ptr(feat_in), _l.dtype_code(feat_in), feat_in.shape[0], _l.ptr(w_packed), _l.ptr(rb.nbr), rb.nbr.shape[1], K,
-                                    _l.ptr(n_out_dev), cap_out, _l.ptr(y), _l.ptr(scale), _l.ptr(shift), _l.ptr(residual), _l.ptr(addend),
-                                    int(bool(relu)), HINT_ROWS_RANKED if ranked else 0, Cin, Cout, _l.ptr(hi), _l.ptr(lo), _l.stream())
-    _l.check(rc, "fnp_spconv_forward_split")
+    route = forward_route(rb, K, Cin, Cout, feat_in.dtype, None, feat_in.shape[0], ranked, tile, split=True)
+    rows, table = (_l.ptr(feat_in), _l.dtype_code(feat_in), feat_in.shape[0], _l.ptr(w_packed)), (_l.ptr(rb.nbr), rb.nbr.shape[1])   # (as in conv_forward)
+    dst, epilogue = (_l.ptr(n_out_dev), cap_out, _l.ptr(y)), (_l.ptr(scale), _l.ptr(shift), _l.ptr(residual), _l.ptr(addend), int(bool(relu)))
+    tail = (Cin, Cout, _l.ptr(hi), _l.ptr(lo), _l.stream())
+    if route == ROUTE_TILED:
+        rc = L.fnp_spconv_forward_tiled_split(*rows, _l.ptr(tile_rulebook(rb, n_out_dev, Cin)), *table, *dst, *epilogue, *tail)
+    elif route == ROUTE_SORTED:
+        rc = L.fnp_spconv_forward_sorted_split(*rows, *table, _l.ptr(rb._sorted[0]), _l.ptr(rb._sorted[1]), *dst, *epilogue, *tail)
+    else:
+        rc = L.fnp_spconv_forward_split(*rows, *table, K, *dst, *epilogue, HINT_ROWS_RANKED if ranked else 0, *tail)
+    _l.check(rc, "fnp_spconv_forward_split" if route == ROUTE_PLAIN else f"fnp_spconv_forward_{route}_split")
     return y, hi, lo
 
 
@@ -985,6 +1008,14 @@ def rulebook_transpose(rb, n_out_dev, cap_in):
                                   _l.stream())
     _l.check(rc, "fnp_rulebook_transpose")
     return nbr_t
+
+
+def transposed_table(rb, n_out_dev, cap_in):
+    """rulebook_transpose, made on first use and kept with the rulebook (`rb._nbr_t`: one per layer), remade when the input's
+    row count differs."""
+    if rb._nbr_t is None or rb._nbr_t.shape[1] != cap_in:
+        rb._nbr_t = rulebook_transpose(rb, n_out_dev, cap_in)
+    return rb._nbr_t
 
 
 def conv_dgrad(grad_out, w_packed, nbr_t, n_in_dev, cap_in, pretransposed=False):
@@ -1057,8 +1088,8 @@ def conv_wgrad(feat_in, grad_out, rb, n_out_dev, Cin, Cout, pairs=None, module_s
     use_pairs = pairs is None or pairs
     mfma_pairs = (Cin, Cout) in WGRAD_PAIR_SHAPES and feat_in.dtype in (torch.bfloat16, torch.float16) and grad_out.dtype == feat_in.dtype
     small_pairs = Cin * Cout <= 128 and feat_in.dtype == torch.float32 and grad_out.dtype == torch.float32   # (conv_input: 3.6 of 27 neighbours per row)
-    if use_pairs and (mfma_pairs or small_pairs) and rb.nbr is not None and not getattr(rb, "_lean", False):
-        pr = getattr(rb, "_pairs", None) or rulebook_pairs(rb, n_out_dev, rows=cap)
+    if use_pairs and (mfma_pairs or small_pairs) and rb.nbr is not None and not rb._lean:
+        pr = rb._pairs or rulebook_pairs(rb, n_out_dev, rows=cap)
         rc = L.fnp_spconv_wgrad_pairs(_l.ptr(feat_in), _l.dtype_code(feat_in), _l.ptr(grad_out), _l.dtype_code(grad_out), _l.ptr(pr[0]), _l.ptr(pr[1]),
                                       _l.ptr(pr[2]), pr[0].shape[1], rb.K, _l.ptr(n_out_dev), min(cap, pr[0].shape[1]), _l.ptr(dw), layout, Cin, Cout, _l.ptr(ws), ws.numel(),
                                       _l.stream())

@@ -74,18 +74,15 @@ class SparseConvFunction(torch.autograd.Function):
                 # offset k  <=>  o is the neighbour of i at offset K-1-k): same table, weight slabs in mirrored order.
                 # That identity needs a centred kernel (every size odd); an even size takes the transposed table below.
                 wt = ctx.w_mirror if ctx.mirror == 2 else wp.flip(0).transpose(1, 2).contiguous()
-                if ctx.ranked and Cin == Cout and (S.tiled_by_default(Cin, feats.dtype, rb.cap_out) or getattr(rb, "_sorted", None) is not None):
+                if ctx.ranked and Cin == Cout and (S.tiled_by_default(Cin, feats.dtype, rb.cap_out) or rb._sorted is not None):
                     # ... and on the tile rulebook (or the class-sorted sweep) where the forward ran on it
                     dx = S.conv_forward(grad_out, wt, rb, n_in_dev, ranked=True)
                 else:
                     dx = S.conv_dgrad(grad_out, wt, rb.nbr, n_in_dev, feats.shape[0], pretransposed=True)
             else:
-                if getattr(rb, "_nbr_t", None) is None or rb._nbr_t.shape[1] != feats.shape[0]:
-                    rb._nbr_t = S.rulebook_transpose(rb, n_out_dev, feats.shape[0])   # (kept with the rulebook: one per layer)
-                if ctx.mirror == 3:
-                    dx = S.conv_dgrad(grad_out, ctx.w_mirror, rb._nbr_t, n_in_dev, feats.shape[0], pretransposed=True)
-                else:
-                    dx = S.conv_dgrad(grad_out, wp, rb._nbr_t, n_in_dev, feats.shape[0])
+                pre = ctx.mirror == 3      # (the forward's launch wrote the transposed slabs)
+                dx = S.conv_dgrad(grad_out, ctx.w_mirror if pre else wp, S.transposed_table(rb, n_out_dev, feats.shape[0]), n_in_dev, feats.shape[0],
+                                  pretransposed=pre)
         if ctx.needs_input_grad[1]:
             dw = S.conv_wgrad(feats, grad_out, rb, n_out_dev, Cin, Cout, module_shape=weight.shape).to(weight.dtype)   # (f32: no copy)
         return dx, dw, None, None, None, None, None, None
@@ -377,7 +374,7 @@ class SparseInverseConv3d(SparseConvolution):
     def forward(self, input: SparseConvTensor):
         assert isinstance(input, SparseConvTensor)
         rb = input.find_indice_pair(self.indice_key)
-        if rb is None or getattr(rb, "_in_side", None) is None or rb.nbr is None:
+        if rb is None or rb._in_side is None or rb.nbr is None:
             raise ValueError(f"SparseInverseConv3d(indice_key={self.indice_key!r}): no SparseConv3d with this indice_key has run on the way here")
         if torch.is_grad_enabled() and (self.weight.requires_grad or input.features.requires_grad):
             raise NotImplementedError("SparseInverseConv3d: inference only (training the UNet decoder is outside the hot path)")
@@ -389,10 +386,7 @@ class SparseInverseConv3d(SparseConvolution):
             feats = feats.to(torch.bfloat16)
         feats = feats.contiguous()
         cap_in = max(in_idx.shape[0], 1)
-        nbr_t = getattr(rb, "_nbr_t", None)
-        if nbr_t is None or nbr_t.shape[1] != cap_in:
-            nbr_t = rb._nbr_t = S.rulebook_transpose(rb, rb.out_n, cap_in)
-        rbt = S.Rulebook(nbr=nbr_t, K=rb.K, cap_out=cap_in, geom=rb.geom)
+        rbt = S.Rulebook(nbr=S.transposed_table(rb, rb.out_n, cap_in), K=rb.K, cap_out=cap_in, geom=rb.geom)
         out_feats = S.conv_forward(feats, self.packed_weight(feats.dtype), rbt, n_in_dev, tile=False)[: in_idx.shape[0]]
         if self.bias is not None:
             out_feats = out_feats + self.bias.to(out_feats.dtype)

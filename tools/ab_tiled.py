@@ -54,7 +54,7 @@ for tag, rb, n_dev in log:
         w = (torch.randn((K, cout, cin), device=dev) * 0.05).to(torch.bfloat16)
         sc, sh = torch.rand(cout, device=dev) + 0.5, torch.randn(cout, device=dev) * 0.1
         resid = torch.randn((rb.cap_out, cout), device=dev).to(torch.bfloat16)
-        rb.__dict__.pop("_sorted", None)
+        rb._sorted = None
         S.classsort(rb, n_dev, 128)
         perm, bmask = rb._sorted[:2]
         outs = {k: torch.zeros((rb.cap_out, cout), dtype=torch.bfloat16, device=dev) for k in libs}

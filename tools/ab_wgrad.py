@@ -41,7 +41,7 @@ for tag, rb, n_dev in log:
     if not (ranked and K == 27 and cin == cout and cin in want) or cin in seen:
         continue
     n = int(n_dev.item())
-    if rb.nbr is None or getattr(rb, "_lean", False):
+    if rb.nbr is None or rb._lean:
         # the engine's lean table: rebuild the full one from the stage's coordinates is not available here -> transpose-free fallback
         print(json.dumps({"channels": cin, "skipped": "lean table"})); continue
     seen.add(cin)

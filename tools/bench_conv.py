@@ -45,7 +45,7 @@ for tag, rb, n_dev in log:
     resid = None if args.no_residual else torch.randn((rb.cap_out, cout), device=dev).to(TD)
     n_full = n
     if (cin, cout, K) == (128, 128, 27) and args.sort != "auto":
-        rb.__dict__.pop("_sorted", None)
+        rb._sorted = None
         if args.sort == "identity":
             rb._sorted = (torch.arange(rb.cap_out, dtype=torch.int32, device=dev), torch.full((rb.cap_out // 16 + 1,), (1 << 27) - 1, dtype=torch.int32, device=dev))
         if args.sort == "fake18":   # timing probe (wrong results): natural order, every tile sweeps offsets 9..26 only

@@ -47,7 +47,7 @@ def main():
     tag, rb, n_dev = [e for e in log if e[0][:3] == (128, 128, 27)][0]
     n = int(n_dev.item())
     nbr, stride = rb.nbr, rb.nbr.shape[1]
-    assert getattr(rb, "_sorted", None) is not None, "the class sort did not run at this size"
+    assert rb._sorted is not None, "the class sort did not run at this size"
     rowmask = rb._rowmask[:n].to(torch.int64) & 0x7ffffff
     above, below = (rowmask >> 18) != 0, (rowmask & 0x1ff) != 0
     zclass = torch.where(above & below, 2, torch.where(above, 1, torch.where(below, 3, 0)))   # [none | above only | both | below only]
