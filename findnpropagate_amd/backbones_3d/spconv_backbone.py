@@ -13,8 +13,10 @@ Mirrors pcdet/models/backbones_3d/spconv_backbone.py: same constructor signature
     single host sync at the end to size the returned tensors.  `forward_points` additionally
     fuses voxelisation + MeanVFE in front (points never leave the device).
 """
+from collections import namedtuple
 from functools import partial
 
+import itertools
 import os
 import torch
 import torch.nn as nn
@@ -283,6 +285,7 @@ class VoxelResBackBone8x(_BackboneBase):
         self.num_point_features = 128
         self.backbone_channels = {'x_conv1': 16, 'x_conv2': 32, 'x_conv3': 64, 'x_conv4': 128}
         self._engine = None
+        self._iter_pipeline = None    # forward_points_iter: (key, PointsPipeline) of its last call
 
     # ---------------------------------------------------------------- reference contract
     def forward(self, batch_dict):
@@ -335,24 +338,22 @@ class VoxelResBackBone8x(_BackboneBase):
         the same (batch_size, depth, capacity, voxel configuration): the pipeline of the last call is kept (its slots are captured
         graphs and streams picked by test, ~0.5 s to make) and reused.
         capacity: point capacity of a slot (default: sized by the first batch, rounded up to 64 Ki points)."""
-        pipe = None
-        for pts, off in batches:
-            if pipe is None:
-                cap = int(capacity) if capacity else max(65536, (int(pts.shape[0]) + 65535) // 65536 * 65536)
-                key = (int(batch_size), int(depth), cap, int(pts.shape[1]), str(pts.device), bytes(voxel_cfg))
-                kept = self.__dict__.get("_iter_pipeline")
-                if kept is not None and kept[0] == key and int(pts.shape[0]) <= cap:
-                    pipe = kept[1]
-                    while pipe.pending:          # (an iterator of the last call that was dropped half-way)
-                        pipe.result()
-                else:
-                    pipe = PointsPipeline(self, batch_size, voxel_cfg, depth=depth, capacity=cap, n_feat=int(pts.shape[1]))
-                    self.__dict__["_iter_pipeline"] = (key, pipe)
-            if len(pipe.pending) == pipe.depth:
-                yield pipe.result()
-            pipe.submit(pts, off)
-        while pipe is not None and pipe.pending:
-            yield pipe.result()
+        batches = iter(batches)
+        first = next(batches, None)
+        if first is None:
+            return
+        pts = first[0]
+        cap = int(capacity) if capacity else _default_capacity(int(pts.shape[0]))
+        key = (int(batch_size), int(depth), cap, int(pts.shape[1]), str(pts.device), bytes(voxel_cfg))
+        kept = self._iter_pipeline
+        if kept is not None and kept[0] == key and int(pts.shape[0]) <= cap:
+            pipe = kept[1]
+            while pipe.pending:          # (an iterator of the last call that was dropped half-way)
+                pipe.result()
+        else:
+            pipe = PointsPipeline(self, batch_size, voxel_cfg, depth=depth, capacity=cap, n_feat=int(pts.shape[1]))
+            self._iter_pipeline = (key, pipe)
+        yield from pipe.map(itertools.chain([first], batches))
 
 
 # the fused engine's index chain on a side stream (FusedResBackbone._run_once): None = while a hipGraph is being captured (the
@@ -360,6 +361,34 @@ class VoxelResBackBone8x(_BackboneBase):
 # not for stream launches (measured neutral within a box's +-1.5 %: back-to-back launches have no such gaps to hide);
 # FNP_TWO_STREAMS=1 / 0 forces / forbids it everywhere
 TWO_STREAMS = {"0": False, "1": True}.get(os.environ.get("FNP_TWO_STREAMS", ""))
+
+# FusedResBackbone._plan's records.  Stage 1: its rulebook in the compact form; every 16-channel layer on it; the f32 class sort.
+# Stages 2-4: the strided layer resolves its neighbours in the kernel / runs on records; channels of the SubM layers; tile
+# rulebook wanted; table of escape tiles only; class sort (16-bit, f32); escape counter wanted; the tile gate holds the stage off.
+_Plan1 = namedtuple("_Plan1", "ell ell_all srt1")
+_PlanStage = namedtuple("_PlanStage", "fused ell_down ch tiled lean srt srt32 esc no_tile")
+# stages 2-4: (key of the strided layer's prepared weights, of the blocks', the module's sequence)
+_DOWN_STAGES = (('down2', 'blocks2', 'conv2'), ('down3', 'blocks3', 'conv3'), ('down4', 'blocks4', 'conv4'))
+
+
+def _launch_tag(w, residual, ranked):
+    """what a measurement hook calls a convolution launch: (Cin, Cout, K, with residual, on ranked rows) of packed weight w"""
+    return (int(w.shape[2]), int(w.shape[1]), int(w.shape[0]), residual, ranked)
+
+
+def _timed(profile, tag, fn, *args, **kw):
+    """fn(*args, **kw) — one launch — between a pair of timing events, (tag, start, end) appended to `profile`"""
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    y = fn(*args, **kw)
+    e1.record()
+    profile.append((tag, e0, e1))
+    return y
+
+
+def _default_capacity(n):
+    """point capacity of a captured forward sized by its first frame: n rounded up to 64 Ki points"""
+    return max(65536, (n + 65535) // 65536 * 65536)
 
 
 class _PointsGraph:
@@ -387,6 +416,7 @@ class _PointsGraph:
         self.probe, self.deferred = bool(probe), []
         self.host_counts = not self.probe
         self.split_index, self.graph_i, self._index_cut = bool(split_index), None, False
+        self._ctx = None        # the torch.cuda.graph context of the graph being captured (_capture_into)
         self.counts_dev = None
         if self.host_counts:    # (allocated and zeroed HERE: a fill issued during the capture would be a node of the graph)
             self.counts_pin = torch.zeros((32,), dtype=torch.int32, pin_memory=True)
@@ -425,14 +455,11 @@ class _PointsGraph:
         try:
             if self.split_index:
                 self.graph_i = torch.cuda.CUDAGraph()
-                self._ctx = torch.cuda.graph(self.graph_i)
-            else:
-                self._ctx = torch.cuda.graph(self.graph)
-            self._ctx.__enter__()
+            self._capture_into(self.graph_i if self.split_index else self.graph)
             try:
                 self.vox, self.res = self._body(voxel_cfg, capture=True)   # (the engine calls counts_ready() where the counts are final)
             finally:
-                self._ctx.__exit__(None, None, None)
+                self._capture_into(None)
             assert self.counts_dev is not None and (self.deferred or not self.probe), "the engine did not reach its cut"
             assert self._index_cut or not self.split_index, "the engine did not cut behind its index chain"
         finally:
@@ -459,19 +486,24 @@ class _PointsGraph:
         if not self.split_index or self._index_cut:
             return
         self._index_cut = True
-        self._ctx.__exit__(None, None, None)
-        self._ctx = torch.cuda.graph(self.graph, pool=self.graph_i.pool())
-        self._ctx.__enter__()
+        self._capture_into(self.graph, pool_of=self.graph_i)
 
     def counts_ready(self, counts_dev):
         """called by the engine where the counts are final (every forked stream rejoined).  A probe: ends the first graph's capture
         and begins the second's on the same capture stream and memory pool (host counts: nothing to cut)"""
         self.counts_dev = counts_dev
-        if self.host_counts:
-            return
-        self._ctx.__exit__(None, None, None)
-        self._ctx = torch.cuda.graph(self.graph_b, pool=(self.graph_i if self.split_index else self.graph).pool())
-        self._ctx.__enter__()
+        if not self.host_counts:
+            self._capture_into(self.graph_b, pool_of=self.graph_i if self.split_index else self.graph)
+
+    def _capture_into(self, graph, pool_of=None):
+        """the one place the capture moves from graph to graph: ends the capture that is running, if any, and begins `graph`'s
+        (None: none) on the same capture stream, in the memory pool of `pool_of`, a graph captured before"""
+        if self._ctx is not None:
+            self._ctx.__exit__(None, None, None)
+            self._ctx = None
+        if graph is not None:
+            self._ctx = torch.cuda.graph(graph, pool=None if pool_of is None else pool_of.pool())
+            self._ctx.__enter__()
 
     def replay(self, profile=None, conv_stream=None):
         """one forward.  probe graphs: first half, the deferred launches (each between two timing events appended to `profile`
@@ -487,9 +519,7 @@ class _PointsGraph:
         if self.split_index:
             self.graph_i.replay()
             if conv_stream is not None and conv_stream != cur:
-                ev = torch.cuda.Event()
-                ev.record(cur)
-                conv_stream.wait_event(ev)
+                conv_stream.wait_event(cur.record_event())
                 with torch.cuda.stream(conv_stream):
                     self._replay_convs(profile)
                 return
@@ -506,11 +536,7 @@ class _PointsGraph:
                 if profile is None:
                     launch()
                 else:
-                    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                    e0.record()
-                    launch()
-                    e1.record()
-                    profile.append((tag, e0, e1))
+                    _timed(profile, tag, launch)
             self.graph_b.replay()
         self.done_event.record()
         self.engine._last_done = self.done_event     # an eager forward issued next, on any stream, waits for this replay
@@ -540,13 +566,9 @@ class _PointsGraph:
 
     def _body(self, voxel_cfg, capture=False):
         e = self.engine
-        e._ensure_clean()
-        e._dirty = True
-        grids = e._get_grids(self.batch_size, self.pts.device)
-        vox = S.voxelize(self.pts, self.off, self.batch_size, voxel_cfg, grid=grids[0], workspace=e._vox_ws)
-        e._vox_ws = vox['workspace']
-        res = e._run_once(vox['mean'], vox['coords'], vox['n'], self.batch_size, grids[0], sync=False, n_cells=vox['n_cells'],
-                          probe=self if capture else None)
+        vox, grid1 = e._voxelize(self.pts, self.off, self.batch_size, voxel_cfg)
+        res = e._run_once(vox['mean'], vox['coords'], vox['n'], self.batch_size, grid1, sync=False, n_cells=vox['n_cells'],
+                          capture=self if capture else None)
         return vox, res
 
 
@@ -623,7 +645,7 @@ class PointsPipeline:
             for e in self.engines:
                 e.two_streams = False      # (the index chain must sit on the capture stream itself: it becomes a graph of its own)
         self.slots = [None] * self.depth      # _PointsGraph per slot, captured on first use
-        self.pending = []                     # (slot, event, host counts, inputs) in submission order
+        self.pending = []                     # (slot, inputs) in submission order
         self.next_slot = 0
 
     def _graph(self, d):
@@ -631,7 +653,7 @@ class PointsPipeline:
         e.prepare()
         e._gate_tick()        # (a replayed frame counts the tile gate's period down like an eager one)
         g = self.slots[d]
-        if g is None or g.cap_factor != e._graph_key() or g.prep_key != e._prep_key:
+        if e._stale(g):
             torch.cuda.synchronize(self.device)   # (capture: nothing else of this pipeline may be in flight)
             g = _PointsGraph(e, self.capacity, self.n_feat, self.batch_size, self.cfg, self.device, probe=self.probe, split_index=self.serial_convs)
             self.slots[d] = g
@@ -654,25 +676,19 @@ class PointsPipeline:
             g.replay(self.profile if self.probe else None, conv_stream=self.conv_stream)
         points.record_stream(st)
         batch_offsets.record_stream(st)
-        self.pending.append((d, None, (points, batch_offsets)))
+        self.pending.append((d, (points, batch_offsets)))
 
     def result(self):
         """the oldest frame in flight: the dict of forward_points_graphed.  Waits for that frame only."""
-        d, _, (points, batch_offsets) = self.pending.pop(0)
+        d, (points, batch_offsets) = self.pending.pop(0)
         g, e = self.slots[d], self.engines[d]
         counts = g.counts()
-        ev = g.done_event
         overflow = e._digest_counts(counts, g.res['ell_used'], g.res['caps'])
-        torch.cuda.current_stream(self.device).wait_event(ev)   # the caller's stream reads the slot's buffers next
+        torch.cuda.current_stream(self.device).wait_event(g.done_event)   # the caller's stream reads the slot's buffers next
         if overflow:
-            # a capacity was too small for this frame (and has been grown): the engine's own loop recaptures (synchronously; rare)
-            ev.synchronize()
-            for pd, _, _ in self.pending:
-                self.slots[pd].done_event.synchronize()
-            torch.cuda.synchronize(self.device)
-            for gr in e._get_grids(self.batch_size, self.device):   # rows beyond a capacity were never emitted: the sparse clear missed their cells
-                gr.zero_()
-            e._dirty = False
+            # a capacity was too small for this frame (and has been grown): the engine's own loop recaptures (synchronously; rare;
+            # the wipe waits for the whole device, the other slots' frames in flight included)
+            e._wipe_after_overflow(self.batch_size, self.device)
             self.slots[d] = None
             return e.run_points_graphed(points, batch_offsets, self.batch_size, self.cfg, self.capacity)
         return e._results(g.res['stages'], counts, g.res['shapes'], self.batch_size, vox=g.vox)
@@ -701,9 +717,10 @@ class FusedResBackbone:
         # convolution is three launches of the bf16 kernels with f32 outputs chained through `residual`:
         #   t = lo * W_hi (+ identity);  t = hi * W_lo + t;  y = relu(hi * W_hi + shift + t)
         # (the lo * W_lo term, 2^-16 of a product, is dropped).  conv_input reads the f32 voxel means on the f32 kernel.
-        self.x3 = getattr(module, 'fnp_dtype', '') == 'bf16x3'
+        self.x3 = module.fnp_dtype == 'bf16x3'
         self._prep = None
         self._prep_key = None
+        self._prep_slots = None       # prepare(): where the module keeps its parameters and buffers
         self._grids = {}
         # capacity of stage l (l = 2..5) as a multiple of the stage-1 capacity; grown on overflow
         self.cap_factor = [3.0, 2.0, 1.0, 1.0]
@@ -736,13 +753,14 @@ class FusedResBackbone:
         # is copied behind every forward into a device word that travels with the per-stage counts of the one host sync
 
     def _counts_word(self, stage, ell_used, device, host=None):
-        """enqueue ONE launch that collects what the host reads in a forward's one synchronisation — the five stage counts, the
-        library's time-out counter, the pool counters of the compact rulebooks, in that order — into a fresh int32 tensor.
+        """enqueue ONE launch that collects what the host reads in a forward's one synchronisation — the five stage counts
+        (`stage`: their device words), the library's time-out counter, the pool counters of the compact rulebooks, in that order —
+        into a fresh int32 tensor.
         host = (pinned int32 tensor, device sequence word): the launch also stores them into the pinned tensor and its own number
         behind them (fnp_gather_counts_host: the host polls for that number instead of waiting for an event)"""
         import ctypes
         from .. import lib as _l
-        srcs = [s[2] for s in stage] + [None] + [u for u, _, _ in ell_used]
+        srcs = stage + [None] + [u for u, _, _ in ell_used]
         arr = (ctypes.c_void_p * len(srcs))(*[None if t is None else t.data_ptr() for t in srcs])
         out = torch.empty((len(srcs),), dtype=torch.int32, device=device)
         reset = sum(1 << (len(stage) + 1 + i) for i in range(len(ell_used)))   # the pool counters are the engine's: zero for the next forward
@@ -862,7 +880,7 @@ class FusedResBackbone:
         #  the module tree (m.parameters() + m.buffers(): ~0.1 ms of a 0.45 ms one-scene forward) is done once, what is read per call
         #  are the (container, name) slots it found — .to() / load_state_dict replace the tensors IN those containers.  The module's
         #  structure is fixed at construction.)
-        slots = getattr(self, "_prep_slots", None)
+        slots = self._prep_slots
         if slots is None:
             slots = self._prep_slots = ([(mod._parameters, k) for mod in m.modules() for k, v in mod._parameters.items() if v is not None] +
                                         [(mod._buffers, k) for mod in m.modules() for k, v in mod._buffers.items() if v is not None])
@@ -968,32 +986,38 @@ class FusedResBackbone:
     def run_points(self, points, batch_offsets, batch_size, voxel_cfg, sync=True):
         if points.is_cuda and self._last_done is not None and not torch.cuda.is_current_stream_capturing():
             torch.cuda.current_stream(points.device).wait_event(self._last_done)   # (see _run_once: forwards return early)
+        vox, grid1 = self._voxelize(points, batch_offsets, batch_size, voxel_cfg)
+        res = self.run(vox['mean'], vox['coords'], vox['n'], batch_size, grid1=grid1, sync=sync, n_cells=vox['n_cells'], vox=vox)
+        if not sync:     # (no counts on the host: the voxeliser's outputs as they are, uncut)
+            res['voxel_coords'], res['voxel_num_points'], res['voxel_features'] = vox['coords'], vox['num_points'], vox['mean']
+        return res
+
+    def _voxelize(self, points, batch_offsets, batch_size, voxel_cfg):
+        """voxelisation + MeanVFE into the engine's stage-1 grid: (the voxeliser's outputs, that grid) for _run_once"""
         self._ensure_clean()
         self._dirty = True
         grids = self._get_grids(batch_size, points.device)
         vox = S.voxelize(points, batch_offsets, batch_size, voxel_cfg, grid=grids[0], workspace=self._vox_ws)
         self._vox_ws = vox['workspace']
-        res = self.run(vox['mean'], vox['coords'], vox['n'], batch_size, grid1=grids[0], sync=sync, n_cells=vox['n_cells'])
-        res['voxel_coords'], res['voxel_num_points'], res['voxel_features'] = vox['coords'], vox['num_points'], vox['mean']
-        if sync:
-            n1 = res['counts'][0]
-            res['voxel_coords'] = vox['coords'][:n1]
-            res['voxel_num_points'] = vox['num_points'][:n1]
-            res['voxel_features'] = vox['mean'][:n1]
-        return res
+        return vox, grids[0]
+
+    def _stale(self, g):
+        """must the captured forward `g` (a _PointsGraph or None) be captured anew?  It bakes in the capacities, the tile gate's
+        state and the prepared weights"""
+        return g is None or g.cap_factor != self._graph_key() or g.prep_key != self._prep_key
 
     def run_points_graphed(self, points, batch_offsets, batch_size, voxel_cfg, capacity=None, probe=False):
         # probe: the two-graph form of _PointsGraph; self.profile (a list) then receives the event pairs of the launches between
         assert (self.profile is None or probe) and self.rulebook_log is None, "measurement hooks are not capturable"
         n, C = points.shape
-        capacity = int(capacity) if capacity else max(65536, (n + 65535) // 65536 * 65536)
+        capacity = int(capacity) if capacity else _default_capacity(n)
         assert n <= capacity
         self.prepare()
         key = (batch_size, capacity, C, str(points.device), bool(probe))
         self._gate_tick()
         while True:
             g = self._graphs.get(key)
-            if g is None or g.cap_factor != self._graph_key() or g.prep_key != self._prep_key:
+            if self._stale(g):
                 prof, self.profile = self.profile, None   # (the capture itself is not a measurement)
                 try:
                     g = _PointsGraph(self, capacity, C, batch_size, voxel_cfg, points.device, probe=probe)
@@ -1005,24 +1029,53 @@ class FusedResBackbone:
             counts = g.counts()   # the one host sync: the counts the graph's counts launch stored (a probe: their copy between its two graphs)
             if not self._digest_counts(counts, g.res['ell_used'], g.res['caps']):
                 break
-            torch.cuda.synchronize(points.device)                  # (the second graph of the failed forward may still be running)
-            for gr in self._get_grids(batch_size, points.device):   # see _run_once: the sparse clear missed cells
-                gr.zero_()
+            self._wipe_after_overflow(batch_size, points.device)
             del self._graphs[key]                                  # recapture with the larger buffers
         return self._results(g.res['stages'], counts, g.res['shapes'], batch_size, vox=g.vox)
 
-    def run(self, feats, indices, n1, batch_size, grid1=None, sync=True, n_cells=None, final_dtype=None):
+    def run(self, feats, indices, n1, batch_size, grid1=None, sync=True, n_cells=None, final_dtype=None, vox=None):
         """feats (cap1,Cin) f32, indices (cap1,4) i32, n1 (1,) i32 device.
         n_cells: rows [n1, n_cells) of indices list further cells set in grid1 (voxels the voxeliser dropped).
-        final_dtype: dtype conv_out writes (default: the engine's activation dtype)."""
+        final_dtype: dtype conv_out writes (default: the engine's activation dtype).
+        vox: the voxeliser's outputs the rows came from (run_points), returned cut to the stage-1 count like the stages."""
         while True:
-            res = self._run_once(feats, indices, n1, batch_size, grid1, sync, n_cells, final_dtype)
+            res = self._run_once(feats, indices, n1, batch_size, grid1, sync, n_cells, final_dtype, None, vox)
             if res is not None:
                 return res
             # overflow: capacities were grown and grids cleared; rebuild grid1 from the indices
             grid1 = None
 
-    def _run_once(self, feats, indices, n1, batch_size, grid1, sync, n_cells=None, final_dtype=None, probe=None):
+    def _conv(self, x, prm, rb, n, residual=None, out_dtype=None, ranked=False, want_f32=True):
+        """one layer of the forward: convolution + BatchNorm(eval) + (residual) + ReLU on the kernel its rulebook has
+        (out_dtype: default the activation dtype)"""
+        if self.x3 and isinstance(prm[0], tuple):
+            return self._conv_x3(x, prm, rb, n, residual, ranked, want_f32)
+        w, sc, sh = prm
+        out_dtype = out_dtype or self.act
+        tag = _launch_tag(w, residual is not None, ranked)
+        if self.rulebook_log is not None:
+            self.rulebook_log.append((tag, rb, n))
+        if rb._ell is not None and (rb.nbr is None or int(w.shape[2]) <= 8):   # on the compact rulebook
+            fn, args, kw = S.conv_forward_ell, (x, w, rb, n), dict(out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True)
+        elif rb.nbr is None:   # fused strided layer
+            fn, args, kw = S.conv_forward_strided, (x, w, rb), dict(scale=sc, shift=sh, relu=True)
+        else:
+            fn, args, kw = S.conv_forward, (x, w, rb, n), dict(out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True, ranked=ranked)
+        if self.profile is None or (self.profile_only is not None and tag[:3] not in self.profile_only):
+            return fn(*args, **kw)
+        return _timed(self.profile, tag, fn, *args, **kw)
+
+    def _blocks(self, x, rb, n, prms, ranked=False):
+        """the residual blocks of one stage"""
+        for p1, p2 in prms:
+            t = self._conv(x, p1, rb, n, ranked=ranked, want_f32=False)     # (bf16x3: only the split of t is read)
+            x = self._conv(t, p2, rb, n, residual=x, ranked=ranked)
+        return x
+
+    def _run_once(self, feats, indices, n1, batch_size, grid1, sync, n_cells=None, final_dtype=None, capture=None, vox=None):
+        """one forward in three phases: the plan (_plan: every decision, as data), the index chain (_index_chain), the
+        convolutions (_convolutions).  capture: the _PointsGraph that is capturing this forward; vox: the voxeliser's outputs,
+        cut with the stages'.  None: a capacity overflowed and has been grown (run() repeats the forward)."""
         # The persistent rank grids must be all-zero on entry and are only cleared sparsely at the end of a run: if a
         # previous run died in between (FnpError, out of memory, KeyboardInterrupt), wipe them before they are reused
         # (run_points checks before it voxelises into grid1)
@@ -1034,7 +1087,7 @@ class FusedResBackbone:
         capturing = feats.is_cuda and torch.cuda.is_current_stream_capturing()
         # (bf16x3 parameters are ((W_hi, W_lo, ones), None, shift) triples and a layer is several launches: the per-launch
         #  measurement hooks and the probe's deferred launches are written for the one-launch engines)
-        assert not (self.x3 and (self.profile is not None or self.rulebook_log is not None or (probe is not None and probe.probe))), \
+        assert not (self.x3 and (self.profile is not None or self.rulebook_log is not None or (capture is not None and capture.probe))), \
             "bf16x3: profile / rulebook_log / probe graphs are not supported (time the whole forward instead: tools/bench_x3.py)"
         if feats.is_cuda and not capturing and self._last_done is not None:
             torch.cuda.current_stream(feats.device).wait_event(self._last_done)
@@ -1049,49 +1102,7 @@ class FusedResBackbone:
         if grid1 is None:
             grid1 = S.build_grid(indices, n1, batch_size, m.sparse_shape, keep_order=True, grid=grids[0])
         caps = [cap1] + [max(256, int(cap1 * f)) for f in self.cap_factor]
-
-        def timed(tag, fn, *args, **kw):   # (profile: one launch between a pair of timing events; never on the unprofiled path)
-            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-            e0.record()
-            y = fn(*args, **kw)
-            e1.record()
-            self.profile.append((tag, e0, e1))
-            return y
-
-        def conv(x, prm, rb, n, residual=None, out_dtype=act, ranked=False, want_f32=True):
-            if self.x3 and isinstance(prm[0], tuple):
-                return self._conv_x3(x, prm, rb, n, residual, ranked, want_f32)
-            w, sc, sh = prm
-            tag = (int(w.shape[2]), int(w.shape[1]), int(w.shape[0]), residual is not None, ranked)  # Cin, Cout, K, res
-            if self.rulebook_log is not None:
-                self.rulebook_log.append((tag, rb, n))
-            if rb._ell is not None and (rb.nbr is None or int(w.shape[2]) <= 8):   # on the compact rulebook
-                fn, args, kw = S.conv_forward_ell, (x, w, rb, n), dict(out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True)
-            elif rb.nbr is None:   # fused strided layer
-                fn, args, kw = S.conv_forward_strided, (x, w, rb), dict(scale=sc, shift=sh, relu=True)
-            else:
-                fn, args, kw = S.conv_forward, (x, w, rb, n), dict(out_dtype=out_dtype, scale=sc, shift=sh, residual=residual, relu=True, ranked=ranked)
-            if self.profile is None or (self.profile_only is not None and tag[:3] not in self.profile_only):
-                return fn(*args, **kw)
-            return timed(tag, fn, *args, **kw)
-
-        def blocks(x, rb, n, prms, ranked=False):
-            for p1, p2 in prms:
-                t = conv(x, p1, rb, n, ranked=ranked, want_f32=False)     # (bf16x3: only the split of t is read)
-                x = conv(t, p2, rb, n, residual=x, ranked=ranked)
-            return x
-
-        # stage 1 (conv_input + conv1): one SubM rulebook serves indice_keys 'subm1' and 'res1'.  16-bit engines: the rulebook
-        # kernel writes the compact form only (32 bytes per row, the neighbours that exist; no (27, cap) table): conv_input (5
-        # input channels) sums the records on the VALU (2.3x the table kernel), the four 16 -> 16 layers and the strided
-        # 16 -> 32 layer run the matrix kernel with the records of a tile's rows expanded into LDS at the top of the tile
-        # (fnp_spconv_forward_ell_mfma: the table kernel's values bit for bit, +3 % end to end: the table was 108 of the ~170
-        # bytes such a row moves).  FNP_ELL_MFMA=0: the round's first form — table beside the records, matrix kernels on the
-        # table; FNP_ELL=1 with it: 16-channel rows on the VALU kernel.  f32, and while rulebooks are logged: tables only.
-        ell = (act in (torch.bfloat16, torch.float16) and self.rulebook_log is None and S.ELL_MODE is not False
-               and (int(P['in'][0].shape[2]), 16) in S.ELL_SHAPES and not isinstance(P['in'][0], S.PermutedWeight))
-        ell_used = []
-        ell_all = ell and (S.ELL_MODE is True or (S.ELL_MODE is None and S.ELL_MFMA))
+        plan1, plans = self._plan(P, caps)
 
         # TWO STREAMS (round 3).  Everything that builds indices — rank grids, output coordinates, rulebooks, records, the class
         # sort — depends on coordinates only, never on features: the whole chain of the five stages is enqueued first, on the
@@ -1101,217 +1112,254 @@ class FusedResBackbone:
         # capture only (see TWO_STREAMS above); never while a profile or a rulebook log is being taken.
         two = (self.profile is None and self.rulebook_log is None and feats.is_cuda and self.two_streams
                and (TWO_STREAMS if TWO_STREAMS is not None else torch.cuda.is_current_stream_capturing()))
-        main = torch.cuda.current_stream(dev) if feats.is_cuda else None
-        side = self._side_stream(dev) if two else None
-        events = []
-
-        class _Index:   # index work goes to the side stream; leaving the block records the stage's event
-            def __enter__(ctx):
-                if two:
-                    ctx.cm = torch.cuda.stream(side)
-                    ctx.cm.__enter__()
-                return ctx
-
-            def __exit__(ctx, *exc):
-                if two:
-                    ev = torch.cuda.Event()
-                    ev.record(side)
-                    events.append(ev)
-                    ctx.cm.__exit__(*exc)
-                return False
-
+        fw = _Forward(self, capture, sync, dev, torch.cuda.current_stream(dev) if feats.is_cuda else None,
+                      self._side_stream(dev) if two else None)
+        chain_args = (fw, plan1, plans, indices, n1, grid1, n_cells if n_cells is not None else n1, grids, caps)
         if two:
-            side.wait_stream(main)   # (inputs, and the sparse clear of the previous forward, are the caller's stream's)
+            fw.side.wait_stream(fw.main)   # (inputs, and the sparse clear of the previous forward, are the caller's stream's)
+            with torch.cuda.stream(fw.side):
+                chain = self._index_chain(*chain_args)
+        else:
+            chain = self._index_chain(*chain_args)
+        if capture is not None and capture.split_index:
+            assert not two, "a split capture keeps its index chain on the capture stream"
+            capture.index_ready()      # (_PointsGraph: the voxeliser + index chain are a graph of their own)
+        stage = self._convolutions(fw, P, feats, indices, n1, grid1, final_dtype or act, *chain)
+        self._dirty = False
+        self._record_done(feats, capturing)
 
-        # ---- index chain ------------------------------------------------------------------------------------------------
-        with _Index():
-            if ell:
-                rb1 = S.rulebook_subm_ell(indices, n1, grid1, int(cap1 * self.ell_pool[0]) + 64, with_table=not ell_all, used=self._ell_counter(0, dev))
-                ell_used.append((rb1._ell[2], rb1._ell[1], 0))
-            else:
-                # (f32: the 16 -> 16 layers sweep their ranges class by class, like every f32 SubM stage below)
-                srt1 = S.f32_sorted_by_default(16, act, cap1) and self.rulebook_log is None and not self.x3
-                rb1 = S.rulebook_subm(indices, n1, grid1, 3, masks=srt1)
-                if srt1:
-                    S.classsort_f32(rb1, n1, 16)
-        idx_prev, n_prev, g_prev = indices, n1, grid1
-        books = []
-        for li, (down_key, blk_key, dconv) in enumerate((('down2', 'blocks2', m.conv2[0][0]),
-                                                          ('down3', 'blocks3', m.conv3[0][0]),
-                                                          ('down4', 'blocks4', m.conv4[0][0]))):
+        shapes = self._stage_shapes()
+        if not sync:
+            return {'stages': stage, 'shapes': shapes, 'caps': caps, 'ell_used': fw.ell_used}
+        fw.counts_ev.synchronize()   # the one host sync: the counts' copy, not the end of the forward
+        counts = self._counts_pin[:fw.counts_dev.numel()].tolist()
+        if self._digest_counts(counts, fw.ell_used, caps):
+            self._wipe_after_overflow(batch_size, dev)
+            self._record_done(feats, capturing)     # (a caller on another stream must come behind the wipe too)
+            return None
+        return self._results(stage, counts, shapes, batch_size, vox=vox)
+
+    def _record_done(self, feats, capturing):
+        """(a forward returns before the GPU has finished it: the next one, on whatever stream, waits for this event)"""
+        if feats.is_cuda and not capturing:
+            self._last_done = torch.cuda.current_stream(feats.device).record_event()
+
+    def _wipe_after_overflow(self, batch_size, device):
+        """a forward overflowed a capacity (grown since): rows beyond a capacity were never emitted, so the sparse clear
+        missed their cells — wipe the persistent grids before the retry with larger buffers.  (Synchronised first: the rest of
+        the failed forward, a graph's second half or another slot's, may still be running.)  Dropping the stale graph is the
+        caller's."""
+        torch.cuda.synchronize(device)
+        for g in self._get_grids(batch_size, device):
+            g.zero_()
+        self._dirty = False
+
+    def _plan(self, P, caps):
+        """Every decision of one forward, as data: (stage 1's _Plan1, [the _PlanStage of stages 2, 3, 4]).  From the prepared
+        weights' shapes, the engine's dtype, the capacities, the tile gate, whether rulebooks are logged and the switches of
+        sparse.py; allocates nothing, launches nothing."""
+        m, act, logged = self.m, self.act, self.rulebook_log is not None
+        half = act in (torch.bfloat16, torch.float16)
+        # stage 1 (conv_input + conv1): one SubM rulebook serves indice_keys 'subm1' and 'res1'.  16-bit engines: the rulebook
+        # kernel writes the compact form only (32 bytes per row, the neighbours that exist; no (27, cap) table): conv_input (5
+        # input channels) sums the records on the VALU (2.3x the table kernel), the four 16 -> 16 layers and the strided
+        # 16 -> 32 layer run the matrix kernel with the records of a tile's rows expanded into LDS at the top of the tile
+        # (fnp_spconv_forward_ell_mfma: the table kernel's values bit for bit, +3 % end to end: the table was 108 of the ~170
+        # bytes such a row moves).  FNP_ELL_MFMA=0: the round's first form — table beside the records, matrix kernels on the
+        # table; FNP_ELL=1 with it: 16-channel rows on the VALU kernel.  f32, and while rulebooks are logged: tables only.
+        ell = (half and not logged and S.ELL_MODE is not False
+               and (int(P['in'][0].shape[2]), 16) in S.ELL_SHAPES and not isinstance(P['in'][0], S.PermutedWeight))
+        ell_all = ell and (S.ELL_MODE is True or (S.ELL_MODE is None and S.ELL_MFMA))
+        # (f32: the 16 -> 16 layers sweep their ranges class by class, like every f32 SubM stage below)
+        srt1 = not ell and S.f32_sorted_by_default(16, act, caps[0]) and not logged and not self.x3
+        act_k = torch.bfloat16 if self.x3 else act     # (bf16x3: its cross terms run on the bf16 engine's kernels)
+        plans = []
+        for li, (down_key, blk_key, seq) in enumerate(_DOWN_STAGES):
             # the down-sampling layers resolve their neighbours inside the convolution (their rulebook has no other
             # user): no (27, cap) table; the table path stays for f32 and when the rulebooks are being logged
-            wd = P[down_key][0]
-            fused = (act in (torch.bfloat16, torch.float16) and self.rulebook_log is None and tuple(dconv.kernel_size) == (3, 3, 3)
-                     and (int(wd.shape[2]), int(wd.shape[1])) in S.FUSED_STRIDED_SHAPES)
-            ell_down = ell_all and li == 0 and tuple(dconv.kernel_size) == (3, 3, 3) and (int(wd.shape[2]), int(wd.shape[1])) in S.ELL_SHAPES
-            with _Index():
-                rbs = S.rulebook_strided(idx_prev, n_prev, g_prev, dconv.kernel_size, dconv.stride, dconv.padding,
-                                         caps[li + 1], out_grid=grids[li + 1], want_nbr=not (fused or ell_down))
-                if ell_down:
-                    S.ell_for_strided(rbs, int(caps[li + 1] * self.ell_pool[1]) + 64, used=self._ell_counter(1, dev))
-                    ell_used.append((rbs._ell[2], rbs._ell[1], 1))
-                # stages 2-4: rows are in rank-grid order on both sides of the SubM convolutions; where they run on the tile
-                # rulebook (stage 2, 32 channels), the rulebook kernel writes it in the same pass
-                w0 = P[blk_key][0][0][0]
-                ch = int((w0[0] if isinstance(w0, tuple) else w0).shape[1])
-                act_k = torch.bfloat16 if self.x3 else act     # (bf16x3: its cross terms run on the bf16 engine's kernels)
-                srt = S.sorted_by_default(ch, ch, act_k, caps[li + 1])
-                tiled = (S.tiled_by_default(ch, act_k, caps[li + 1]) and S.tiled_fits(caps[li + 1], ch, caps[li + 1], caps[li + 1])
-                         and self.tile_off.get(li, 0) <= 0)
-                lean = tiled and self.rulebook_log is None   # (all four layers of the stage run tiled)
-                srt32 = S.f32_sorted_by_default(ch, act, caps[li + 1]) and self.rulebook_log is None and not self.x3
-                esc_ctr = self._ell_counter(("esc", li), dev) if (lean and S.TILE_MODE is None) else None
-                rb = S.rulebook_subm(rbs.out_indices, rbs.out_n, rbs.out_grid, 3, tile_channels=ch if tiled else None, masks=srt or srt32,
-                                     lean_table=lean, esc_counter=esc_ctr)
-                if esc_ctr is not None:
-                    ell_used.append((esc_ctr, None, ("esc", li)))
-                if self.tile_off.get(li, 0) > 0:
-                    rb._no_tile = True
-                if srt:
-                    S.classsort(rb, rbs.out_n, ch)   # stage 4: the 128-channel layers sweep their rows class by class
-                if srt32:
-                    S.classsort_f32(rb, rbs.out_n, ch)   # f32 engine: every stage's ranges in class order
+            wd, cap = P[down_key][0], caps[li + 1]
+            cubic = tuple(getattr(m, seq)[0][0].kernel_size) == (3, 3, 3)
+            # (wd is read behind `half` / `ell_all` only: the bf16x3 engine's is a (W_hi, W_lo, ones) triple)
+            fused = half and not logged and cubic and (int(wd.shape[2]), int(wd.shape[1])) in S.FUSED_STRIDED_SHAPES
+            ell_down = ell_all and li == 0 and cubic and (int(wd.shape[2]), int(wd.shape[1])) in S.ELL_SHAPES
+            # stages 2-4: rows are in rank-grid order on both sides of the SubM convolutions; where they run on the tile
+            # rulebook (stage 2, 32 channels), the rulebook kernel writes it in the same pass
+            w0 = P[blk_key][0][0][0]
+            ch = int((w0[0] if isinstance(w0, tuple) else w0).shape[1])
+            no_tile = self.tile_off.get(li, 0) > 0
+            srt = S.sorted_by_default(ch, ch, act_k, cap)     # stage 4: the 128-channel layers sweep their rows class by class
+            tiled = S.tiled_by_default(ch, act_k, cap) and S.tiled_fits(cap, ch, cap, cap) and not no_tile
+            lean = tiled and not logged   # (all four layers of the stage run tiled)
+            srt32 = S.f32_sorted_by_default(ch, act, cap) and not logged and not self.x3   # f32 engine: every stage's ranges in class order
+            plans.append(_PlanStage(fused, ell_down, ch, tiled, lean, srt, srt32, lean and S.TILE_MODE is None, no_tile))
+        return _Plan1(ell, ell_all, srt1), plans
+
+    def _index_chain(self, fw, plan1, plans, indices, n1, grid1, n_clear, grids, caps):
+        """Phase two: rank grids, the five rulebooks, records, class sorts — and the counts launch of a capture with host counts.
+        Runs with the side stream current when the forward has two (fw.index_done records a stage's event).  Returns
+        (stage 1's rulebook, [(down key, blocks key, strided rulebook, SubM rulebook) of stages 2-4], conv_out's rulebook)."""
+        m, dev, ell_used = self.m, fw.dev, fw.ell_used
+        if plan1.ell:
+            rb1 = S.rulebook_subm_ell(indices, n1, grid1, int(caps[0] * self.ell_pool[0]) + 64, with_table=not plan1.ell_all, used=self._ell_counter(0, dev))
+            ell_used.append((rb1._ell[2], rb1._ell[1], 0))
+        else:
+            rb1 = S.rulebook_subm(indices, n1, grid1, 3, masks=plan1.srt1)
+            if plan1.srt1:
+                S.classsort_f32(rb1, n1, 16)
+        fw.index_done()
+        idx_prev, n_prev, g_prev = indices, n1, grid1
+        books = []
+        for li, (pl, (down_key, blk_key, seq)) in enumerate(zip(plans, _DOWN_STAGES)):
+            dconv, cap = getattr(m, seq)[0][0], caps[li + 1]
+            rbs = S.rulebook_strided(idx_prev, n_prev, g_prev, dconv.kernel_size, dconv.stride, dconv.padding,
+                                     cap, out_grid=grids[li + 1], want_nbr=not (pl.fused or pl.ell_down))
+            if pl.ell_down:
+                S.ell_for_strided(rbs, int(cap * self.ell_pool[1]) + 64, used=self._ell_counter(1, dev))
+                ell_used.append((rbs._ell[2], rbs._ell[1], 1))
+            esc_ctr = self._ell_counter(("esc", li), dev) if pl.esc else None
+            rb = S.rulebook_subm(rbs.out_indices, rbs.out_n, rbs.out_grid, 3, tile_channels=pl.ch if pl.tiled else None, masks=pl.srt or pl.srt32,
+                                 lean_table=pl.lean, esc_counter=esc_ctr)
+            if esc_ctr is not None:
+                ell_used.append((esc_ctr, None, ("esc", li)))
+            if pl.no_tile:
+                rb._no_tile = True
+            if pl.srt:
+                S.classsort(rb, rbs.out_n, pl.ch)
+            if pl.srt32:
+                S.classsort_f32(rb, rbs.out_n, pl.ch)
+            fw.index_done()
             books.append((down_key, blk_key, rbs, rb))
             idx_prev, n_prev, g_prev = rbs.out_indices, rbs.out_n, rbs.out_grid
         oconv = m.conv_out[0]
+        rbo = S.rulebook_strided(idx_prev, n_prev, g_prev, oconv.kernel_size, oconv.stride, oconv.padding, caps[4],
+                                 out_grid=grids[4])
+        fw.count_srcs = [n1] + [b[2].out_n for b in books] + [rbo.out_n]
+        fw.clear_jobs = ([(grid1, indices, n_clear)] + [(b[2].out_grid, b[2].out_indices, b[2].out_n) for b in books]
+                         + [(rbo.out_grid, rbo.out_indices, rbo.out_n)])
+        fw.counts_here("index")
+        fw.index_done()
+        return rb1, books, rbo
+
+    def _convolutions(self, fw, P, feats, indices, n1, grid1, final_dtype, rb1, books, rbo):
+        """Phase three: conv_input, the four stages, conv_out on the caller's stream, each stage behind its index event; the
+        sparse clear of the grids; the counts launch of every form but host counts.  (rb1, books, rbo: what _index_chain
+        returned.)  Returns the five stages' (features, indices, n_dev, grid)."""
+        fw.ready(0)
+        x = self._conv(feats, P['in'], rb1, n1)
+        if self.x3:
+            x = self._split(x, n1)      # (conv_input ran on the f32 kernel: exact; from here on (hi, lo, f32) triples)
+        x = self._blocks(x, rb1, n1, P['blocks1'])
+        stage = [(x[2] if self.x3 else x, indices, n1, grid1)]
+        for li, (down_key, blk_key, rbs, rb) in enumerate(books):
+            fw.ready(li + 1)
+            x = self._conv(x, P[down_key], rbs, rbs.out_n)
+            if li == len(books) - 1:
+                fw.ready(4)            # (every index kernel is behind us; a capture may end only with every forked stream rejoined)
+                fw.joined = True
+                if fw.two and not fw.two_graphs:   # (a two-graph capture is cut right here: no open branch across the cut)
+                    fw.clear_beside()
+                if fw.two_graphs:
+                    x = fw.blocks_deferred(x, rb, rbs.out_n, P[blk_key])
+                else:
+                    fw.counts_here("convs")
+                    x = self._blocks(x, rb, rbs.out_n, P[blk_key], ranked=True)
+            else:
+                x = self._blocks(x, rb, rbs.out_n, P[blk_key], ranked=True)
+            stage.append((x[2] if self.x3 else x, rbs.out_indices, rbs.out_n, rbs.out_grid))
+        # (one-stream captures — the slots of a PointsPipeline — stay LINEAR: with the clear on a branch beside conv_out the runtime's
+        #  fork / join serialised a batch's index graph behind the other batch's convolutions, 13.2 k -> 12.2 k scenes/s at 128 scenes)
+        x = self._conv(x, P['out'], rbo, rbo.out_n, out_dtype=final_dtype)
+        stage.append((x[2] if self.x3 else x, rbo.out_indices, rbo.out_n, rbo.out_grid))
+
+        # leave every persistent grid zeroed for the next call (O(rows) sparse clear, all five grids in one launch)
+        if fw.cleared is not None:
+            fw.main.wait_event(fw.cleared)
+        else:
+            S.clear_grids(fw.clear_jobs)
+        return stage
+
+
+class _Forward:
+    """What one FusedResBackbone._run_once shares between its phases: the two streams and the events between them, where the
+    counts launch goes and what it left, the engine's counters in the order they are read back.  Made and dropped by
+    _run_once; nothing outside the engine sees it."""
+
+    def __init__(self, eng, capture, sync, dev, main, side):
+        self.eng, self.capture, self.sync, self.dev, self.main, self.side, self.two = eng, capture, sync, dev, main, side, side is not None
+        self.events, self.joined, self.cleared = [], False, None      # the stages' index events; every one waited for; the clear's
+        # the engine's counters in the order the counts launch reads them; its output, the event behind its pinned copy; what
+        # it reads and what the sparse clear wipes (set at the end of the index chain)
+        self.ell_used, self.counts_dev, self.counts_ev, self.count_srcs, self.clear_jobs = [], None, None, None, None
+        self.two_graphs = capture is not None and capture.probe       # (_PointsGraph: the last SubM stage between two graphs)
+        # WHERE THE COUNTS LAUNCH GOES, and what follows it (counts_here).
         # HOST COUNTS (_PointsGraph.host_counts): the counts launch stores into pinned host memory itself, so it needs no cut and no
         # event — and it can sit where the STAGE counts are final, at the end of the index chain (on the index branch), instead of behind the
         # strided layer of stage 4: the host has its counts after ~half of a one-scene forward and sizes the outputs, returns, and
         # issues the next frame while the convolutions still run.  (What is not final there is the tiled kernels' time-out counter: in
         # this form a time-out — never seen; the protocol's guard against a hang — raises with the NEXT forward's counts.)
-        early_counts = probe is not None and probe.host_counts
-        counts_box = {}
-        count_srcs = lambda: [(None, None, n1)] + [(None, None, b[2].out_n) for b in books] + [(None, None, rbo.out_n)]
-        with _Index():
-            rbo = S.rulebook_strided(idx_prev, n_prev, g_prev, oconv.kernel_size, oconv.stride, oconv.padding, caps[4],
-                                     out_grid=grids[4])
-            if early_counts:
-                counts_box['dev'] = self._counts_word(count_srcs(), ell_used, dev, host=(probe.counts_pin, probe.counts_seq))
-                probe.counts_ready(counts_box['dev'])
-
-        # ---- convolutions -----------------------------------------------------------------------------------------------
-        if probe is not None and getattr(probe, "split_index", False):
-            assert not two, "a split capture keeps its index chain on the capture stream"
-            probe.index_ready()      # (_PointsGraph: the voxeliser + index chain are a graph of their own)
-        joined, cleared = [False], [None]
-
-        def clear_jobs():
-            jobs = [(grid1, indices, n_cells if n_cells is not None else n1)]
-            jobs += [(b[2].out_grid, b[2].out_indices, b[2].out_n) for b in books]
-            return jobs + [(rbo.out_grid, rbo.out_indices, rbo.out_n)]
-
-        def clear_beside():
-            # the last reader of a rank grid has been issued (the strided layers resolve their neighbours in the input grid; the
-            # layers behind the strided layer of stage 4 run on tables): the sparse clear of all five grids goes to a branch of
-            # its own and runs beside the convolutions that follow instead of behind conv_out, at the end of the chain
-            br = side
-            ev_c = torch.cuda.Event()
-            ev_c.record(main)
-            br.wait_event(ev_c)
-            with torch.cuda.stream(br):
-                S.clear_grids(clear_jobs())
-                cleared[0] = torch.cuda.Event()
-                cleared[0].record(br)
-
-        def ready(i):
-            if two and not joined[0]:
-                main.wait_event(events[i])
-
-        def blocks_deferred(x, rb, n, prms):
-            # (probe: _PointsGraph) the stage's output buffers are allocated in the first graph's pool, the capture is cut, and
-            # the launches are handed over as closures: replay() issues them between the two graphs
-            plan = []
-            for p1, p2 in prms:
-                t = torch.empty((rb.cap_out, int(p1[0].shape[1])), dtype=act, device=dev)
-                y = torch.empty((rb.cap_out, int(p2[0].shape[1])), dtype=act, device=dev)
-                plan.append((x, t, y, p1, p2))
-                x = y
-            counts_now()     # (probe: the capture is cut inside)
-            for xin, t, y, p1, p2 in plan:
-                tag1 = (int(p1[0].shape[2]), int(p1[0].shape[1]), int(p1[0].shape[0]), False, True)
-                tag2 = (int(p2[0].shape[2]), int(p2[0].shape[1]), int(p2[0].shape[0]), True, True)
-                probe.deferred.append((tag1, lambda xin=xin, t=t, p1=p1: S.conv_forward(xin, p1[0], rb, n, out_dtype=act, scale=p1[1], shift=p1[2],
-                                                                                     relu=True, ranked=True, out=t)))
-                probe.deferred.append((tag2, lambda xin=xin, t=t, y=y, p2=p2: S.conv_forward(t, p2[0], rb, n, out_dtype=act, scale=p2[1], shift=p2[2],
-                                                                                          residual=xin, relu=True, ranked=True, out=y)))
-            return x
-
-        # THE COUNTS LEAVE EARLY (round 3, late).  Everything the host reads in a forward's one synchronisation — the five stage
+        # THE COUNTS LEAVE EARLY (round 3, late), every other form.  Everything the host reads in a forward's one synchronisation — the five stage
         # counts, the tiled kernels' time-out counter (their last launch is in stage 3), the pool counters of the compact
         # rulebooks — is final once the index chain is done and the strided layer of stage 4 has been issued: the counts launch
         # and (stream path) their copy to pinned memory go in front of the four 128 -> 128 convolutions, 30 % of the step.  The
         # host then waits for THAT event, sizes the outputs and returns while the GPU is still convolving; the caller's next
         # forward queues up behind it, and the ~0.1 ms the GPU used to idle between two forwards (copy back, Python, the first
         # launches of the next forward) is gone.  The returned tensors are ordinary stream-ordered torch tensors.
-        def counts_now():
-            if early_counts:
-                return
-            cd = counts_box['dev'] = self._counts_word(count_srcs(), ell_used, dev)
-            if probe is not None:
-                probe.counts_ready(cd)          # (a probe _PointsGraph: the first captured graph ends here)
-            elif sync:
-                pin = self._counts_pin
-                if pin is None or pin.numel() < cd.numel():
-                    pin = self._counts_pin = torch.empty((16,), dtype=torch.int32, pin_memory=True)
-                pin[:cd.numel()].copy_(cd, non_blocking=True)
-                counts_box['ev'] = torch.cuda.Event()
-                counts_box['ev'].record()
+        early = capture is not None and capture.host_counts
+        self.counts_at, self.counts_host = ("index", (capture.counts_pin, capture.counts_seq)) if early else ("convs", None)
 
-        ready(0)
-        x = conv(feats, P['in'], rb1, n1)
-        if self.x3:
-            x = self._split(x, n1)      # (conv_input ran on the f32 kernel: exact; from here on (hi, lo, f32) triples)
-        f32_of = (lambda t: t[2]) if self.x3 else (lambda t: t)
-        x1 = blocks(x, rb1, n1, P['blocks1'])
-        stage = [(f32_of(x1), indices, n1, grid1)]
-        x_prev = x1
-        for li, (down_key, blk_key, rbs, rb) in enumerate(books):
-            ready(li + 1)
-            x = conv(x_prev, P[down_key], rbs, rbs.out_n)
-            if li == len(books) - 1:
-                ready(4)            # (every index kernel is behind us; a capture may end only with every forked stream rejoined)
-                joined[0] = True
-                if two and (probe is None or early_counts):   # (a two-graph capture is cut right here: no open branch across the cut)
-                    clear_beside()
-                if probe is not None and probe.probe:
-                    x = blocks_deferred(x, rb, rbs.out_n, P[blk_key])
-                else:
-                    counts_now()
-                    x = blocks(x, rb, rbs.out_n, P[blk_key], ranked=True)
-            else:
-                x = blocks(x, rb, rbs.out_n, P[blk_key], ranked=True)
-            stage.append((f32_of(x), rbs.out_indices, rbs.out_n, rbs.out_grid))
-            x_prev = x
-        # (one-stream captures — the slots of a PointsPipeline — stay LINEAR: with the clear on a branch beside conv_out the runtime's
-        #  fork / join serialised a batch's index graph behind the other batch's convolutions, 13.2 k -> 12.2 k scenes/s at 128 scenes)
-        xo = conv(x_prev, P['out'], rbo, rbo.out_n, out_dtype=final_dtype or act)
-        stage.append((f32_of(xo), rbo.out_indices, rbo.out_n, rbo.out_grid))
+    def index_done(self):
+        """the index work of one stage has been enqueued (on the side stream, if there is one): its event"""
+        if self.two:
+            self.events.append(self.side.record_event())
 
-        # leave every persistent grid zeroed for the next call (O(rows) sparse clear, all five grids in one launch)
-        if cleared[0] is not None:
-            main.wait_event(cleared[0])
-        else:
-            S.clear_grids(clear_jobs())
-        self._dirty = False
-        counts_dev = counts_box['dev']
-        if feats.is_cuda and not capturing:
-            self._last_done = torch.cuda.Event()
-            self._last_done.record()
+    def ready(self, i):
+        """the convolutions of stage i + 1 come next: behind that stage's index work"""
+        if self.two and not self.joined:
+            self.main.wait_event(self.events[i])
 
-        shapes = self._stage_shapes()
-        if not sync:
-            return {'stages': stage, 'shapes': shapes, 'caps': caps, 'batch_size': batch_size, 'counts_dev': counts_dev, 'ell_used': ell_used}
-        counts_box['ev'].synchronize()   # the one host sync: the counts' copy, not the end of the forward
-        counts = self._counts_pin[:counts_dev.numel()].tolist()
-        if self._digest_counts(counts, ell_used, caps):
-            # rows beyond a capacity were never emitted, so the sparse clear missed their cells:
-            # wipe the persistent grids before the retry with larger buffers
-            for g in grids:
-                g.zero_()
-            self._dirty = False
-            if feats.is_cuda and not capturing:
-                self._last_done = torch.cuda.Event()     # (a caller on another stream must come behind the wipe too)
-                self._last_done.record()
-            return None
-        return self._results(stage, counts, shapes, batch_size)
+    def counts_here(self, where):
+        """called at the end of the index chain ("index") and in front of the last SubM stage ("convs"): the counts launch, at the
+        one of the two this forward has it, and what follows it — a capture is told (a two-graph capture is cut there), an
+        eager forward that synchronises copies the counts to pinned memory and records the event it will wait for"""
+        if where != self.counts_at:
+            return
+        eng = self.eng
+        cd = self.counts_dev = eng._counts_word(self.count_srcs, self.ell_used, self.dev, host=self.counts_host)
+        if self.capture is not None:
+            self.capture.counts_ready(cd)
+        elif self.sync:
+            pin = eng._counts_pin
+            if pin is None or pin.numel() < cd.numel():
+                pin = eng._counts_pin = torch.empty((16,), dtype=torch.int32, pin_memory=True)
+            pin[:cd.numel()].copy_(cd, non_blocking=True)
+            self.counts_ev = self.main.record_event()
+
+    def clear_beside(self):
+        """the last reader of a rank grid has been issued (the strided layers resolve their neighbours in the input grid; the
+        layers behind the strided layer of stage 4 run on tables): the sparse clear of all five grids goes to a branch of
+        its own and runs beside the convolutions that follow instead of behind conv_out, at the end of the chain"""
+        br = self.side
+        br.wait_event(self.main.record_event())
+        with torch.cuda.stream(br):
+            S.clear_grids(self.clear_jobs)
+            self.cleared = br.record_event()
+
+    def blocks_deferred(self, x, rb, n, prms):
+        """(two-graph capture) the stage's output buffers are allocated in the first graph's pool, the capture is cut, and
+        the launches are handed over as closures: replay() issues them between the two graphs"""
+        act, dev = self.eng.act, self.dev
+        plan = []
+        for p1, p2 in prms:
+            t = torch.empty((rb.cap_out, int(p1[0].shape[1])), dtype=act, device=dev)
+            y = torch.empty((rb.cap_out, int(p2[0].shape[1])), dtype=act, device=dev)
+            plan.append((x, t, y, p1, p2))
+            x = y
+        self.counts_here("convs")     # (the capture is cut inside)
+        for xin, t, y, p1, p2 in plan:
+            self.capture.deferred.append((_launch_tag(p1[0], False, True),
+                                          lambda xin=xin, t=t, p1=p1: S.conv_forward(xin, p1[0], rb, n, out_dtype=act, scale=p1[1], shift=p1[2],
+                                                                                     relu=True, ranked=True, out=t)))
+            self.capture.deferred.append((_launch_tag(p2[0], True, True),
+                                          lambda xin=xin, t=t, y=y, p2=p2: S.conv_forward(t, p2[0], rb, n, out_dtype=act, scale=p2[1], shift=p2[2],
+                                                                                          residual=xin, relu=True, ranked=True, out=y)))
+        return x

@@ -287,7 +287,69 @@ def engine_cases(rec):
     S.TILE_MODE, S.ELL_MODE, S.ELL_MFMA = None, None, True
 
 
-SECTIONS = {"operator": operator_cases, "limits": limit_cases, "ell": ell_cases, "backward": backward_cases, "engine": engine_cases}
+# ------------------------------------------------------------------------------------------------ (d) the engine under capture
+class _Word:
+    """stands in for a tensor the counts launch is handed by address: the pinned counts (there is no pinned memory without a
+    device) or the device word behind them"""
+
+    def __init__(self, words, cuda):
+        self.shape, self.dtype, self.is_cuda = (words,), torch.int32, cuda
+
+    def is_pinned(self):
+        return not self.is_cuda
+
+    def numel(self):
+        return self.shape[0]
+
+    def data_ptr(self):
+        return 0
+
+    def is_contiguous(self):
+        return True
+
+
+class _Capture:
+    """stands in for the _PointsGraph being captured: what the engine reads of it, and its two cuts written into the trace
+    where the engine makes them"""
+
+    def __init__(self, rec, probe, split_index):
+        self._rec, self.probe, self.host_counts, self.split_index, self.deferred = rec, probe, not probe, split_index, []
+        self.counts_pin, self.counts_seq = _Word(32, False), _Word(1, True)
+
+    def counts_ready(self, counts_dev):
+        self._rec.calls.append(["cut", "counts"])
+
+    def index_ready(self):
+        self._rec.calls.append(["cut", "index"])
+
+
+def engine_capture_cases(rec):
+    """FusedResBackbone._run_once as a _PointsGraph calls it while it captures, in its four forms: one graph with host counts,
+    the two-graph probe form, and each of them with the index chain a graph of its own.  Behind the forward's own launches,
+    after a ["deferred"] marker: the launches the probe form hands over for replay()."""
+    from findnpropagate_amd.backbones_3d import spconv_backbone as SB
+
+    def forward(eng, cap, feats, idx, n1):
+        eng._run_once(feats, idx, n1, 1, None, False, None, None, cap)
+        rec.calls.append(["deferred"])
+        for _, launch in cap.deferred:
+            launch()
+
+    for fnp_dtype in ("bf16", "fp16", "fp32", "bf16x3"):
+        module = SB.VoxelResBackBone8x({"USE_BIAS": False, "FNP_DTYPE": fnp_dtype}, 5, [64, 64, 8]).eval()
+        for cap1 in (3000, 131072):
+            feats, idx = torch.empty((cap1, 5), dtype=torch.float32), torch.empty((cap1, 4), dtype=torch.int32)
+            n1 = torch.empty((1,), dtype=torch.int32)
+            for probe, split in ((False, False), (False, True), (True, False), (True, True)):
+                if fnp_dtype == "bf16x3" and probe:
+                    continue      # (the engine refuses: the deferred launches are written for the one-launch engines)
+                eng, cap = SB.FusedResBackbone(module), _Capture(rec, probe, split)
+                yield (f"capture {fnp_dtype} cap1={cap1} two_graphs={probe} split_index={split}",
+                       _traced(rec, lambda: forward(eng, cap, feats, idx, n1)))
+
+
+SECTIONS = {"operator": operator_cases, "limits": limit_cases, "ell": ell_cases, "backward": backward_cases, "engine": engine_cases,
+            "engine_capture": engine_capture_cases}
 
 
 # ------------------------------------------------------------------------------------------------ the fixture

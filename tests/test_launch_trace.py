@@ -2,7 +2,8 @@
 
 Every forward kernel gives the plain kernel's bits, so only the trace shows which one a call takes: conv_forward and
 conv_forward_split over their arguments and the rulebook's derived state, the 32-bit-offset fall-backs, conv_forward_ell, the
-kernels the backward of SparseConvFunction picks, and the whole launch list of FusedResBackbone.run for every engine dtype.
+kernels the backward of SparseConvFunction picks, and the whole launch list of FusedResBackbone.run for every engine dtype —
+eager, and in the four forms a _PointsGraph captures it (one or two graphs, the index chain a graph of its own or not).
 The comparison is exact: same entry points, same arguments, same order."""
 import pytest
 
