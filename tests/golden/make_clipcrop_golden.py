@@ -8,7 +8,16 @@ the harness gives the reference object a deterministic stand-in encoder (28x28 a
 random projection, defined identically in tests/test_gpu_clipcrop.py); everything else that runs — corner
 projection, integer truncation, on-image test, clipped bounding box, square crop >= 64 px, F.grid_sample,
 softmax, half-precision accumulation over the cameras, arg-max — is the reference's code.
-Images are procedural (function of pixel coordinates) so that they need not be stored."""
+Images are procedural (function of pixel coordinates) so that they need not be stored.
+
+Besides the outputs, every fixture records what the reference's own project_to_camera returned per
+(scene, camera) (`proj_yxz`: the f32 [row, column, depth] of the 8 corners of every box, by wrapping the
+method on the object), the per-box mean probabilities the arg-max is taken over (`probs_mean`, the
+argument of the reference's torch.max call), and the crop list itself: `crop_pair` (M, 2) [box, camera] and
+`crop_rect` (M, 3) [x1, y1, side], read off the arguments of the reference's own grid_sample calls.  `clipcrop_aug_b2.npz` (argument `aug_b2`) is one run with
+batch_size = 2, image_size = [256, 704], a different non-identity img_aug_matrix per camera and scene
+(resize about 0.44 and a crop shift; one camera flipped, one rotated in the image plane), and a
+lidar_aug_matrix with rotation, scaling and translation in scene 1."""
 import importlib
 import os
 import sys
@@ -54,6 +63,146 @@ class FakeClip:
         return (pooled @ self.P).half()        # the real CLIP runs in fp16 on the GPU (clip.load(..., device='cuda'))
 
 
+NAMES = ['car', 'truck', 'construction_vehicle', 'bus', 'trailer', 'barrier', 'motorcycle', 'bicycle', 'pedestrian', 'traffic_cone']
+
+
+def make_head(mod, image_size, rec):
+    """The reference object without its __init__ (which loads CLIP), with recorders around its own methods."""
+    head = object.__new__(mod.CLIPBoxClassification)
+    torch.nn.Module.__init__(head)
+    head.image_order = [2, 0, 1, 5, 3, 4]
+    head.image_size = list(image_size)
+    head.all_class_names = list(NAMES)
+    head.clip = FakeClip()
+    head.text_features = text_features().half()
+    head.min_crop_size = 64
+    head.unif_grid = F.affine_grid(theta=torch.eye(2, 3).unsqueeze(0), size=[1, 3, 224, 224])
+    project, logits = head.project_to_camera, head.get_clip_logits
+
+    def project_rec(batch_dict, points, batch_idx=0, cam_idx=0):
+        out = project(batch_dict, points, batch_idx, cam_idx)
+        rec["proj"][(batch_idx, cam_idx)] = out[0].numpy().copy()          # (8N, 3): row, column, depth
+        rec["at"] = (batch_idx, cam_idx)
+        return out
+
+    def logits_rec(images):
+        a, b = logits(images)
+        rec["probs"].append(a.softmax(dim=-1).float().numpy().copy())     # what forward stores per camera (:350-352)
+        return a, b
+    head.project_to_camera, head.get_clip_logits = project_rec, logits_rec
+    return head
+
+
+def run_forward(head, bd, pd, rec, keep_crops):
+    """forward with three calls watched: torch.max, whose (N, 10) argument is the per-box mean over the cameras (:361-364);
+    F.grid_sample, whose grid's first and last entries give the crop's x1, y1 and side back as integers (:326-334); and
+    torch.tensor of a list of ints, the boxes cropped in the camera just projected (:344)."""
+    plain_max, plain_gs, plain_tensor = torch.max, F.grid_sample, torch.tensor
+    H, W = head.image_size
+
+    def gs_rec(input, grid, *a, **k):
+        g = grid.double()
+        x1, y1 = (g[0, 0, 0, 0] + 1) / 2 * W, (g[0, 0, 0, 1] + 1) / 2 * H
+        side = (g[0, -1, -1, 0] - g[0, 0, 0, 0]) / 2 * W
+        rec["crop_rect"].append([int(round(float(x1))), int(round(float(y1))), int(round(float(side)))])
+        return plain_gs(input, grid, *a, **k)
+
+    def tensor_rec(*a, **k):
+        if a and isinstance(a[0], list) and a[0] and all(isinstance(i, int) for i in a[0]):
+            rec["crop_pair"] += [[i, rec["at"][1]] for i in a[0]]
+        return plain_tensor(*a, **k)
+    F.grid_sample, torch.tensor = gs_rec, tensor_rec
+
+    def max_rec(*a, **k):
+        if k.get("dim") == -1 and a and a[0].dim() == 2 and a[0].shape[1] == 10:
+            rec["probs_mean"].append(a[0].float().numpy().copy())
+        return plain_max(*a, **k)
+    torch.max = max_rec
+    try:
+        head.forward(bd, pd, keep_crops=keep_crops)
+    finally:
+        torch.max, F.grid_sample, torch.tensor = plain_max, plain_gs, plain_tensor
+
+
+def proj_array(rec, b, n):
+    return np.stack([rec["proj"][(b, c)].reshape(n, 8, 3) for c in range(6)], 0).astype(np.float32)   # (6, N, 8, 3)
+
+
+def img_aug_256x704(rng):
+    """(6,4,4): resize ~0.44 and a crop shift per camera; camera 1 flipped left-right, camera 4 rotated by about a degree about
+    the image centre (the [[s R, t], [0, 1]] form ImageAug3D-style pipelines accumulate, acting on (u, v, depth))."""
+    out = np.tile(np.eye(4, dtype=np.float64), (6, 1, 1))
+    for c in range(6):
+        s = rng.uniform(0.43, 0.45)
+        M = np.diag([s, s])
+        t = np.array([-(1600 * s - 704) / 2 + rng.uniform(-3, 3), -(900 * s - 256) + rng.uniform(-4, 0)])
+        if c == 1:                                   # flip: u -> 704 - u
+            M, t = np.diag([-1.0, 1.0]) @ M, np.array([704.0 - t[0], t[1]])
+        if c == 4:                                   # rotation about the centre of the 704 x 256 image
+            th = np.deg2rad(rng.uniform(0.8, 1.6))
+            R = np.array([[np.cos(th), np.sin(th)], [-np.sin(th), np.cos(th)]])
+            ctr = np.array([352.0, 128.0])
+            M, t = R @ M, R @ (t - ctr) + ctr
+        out[c, :2, :2], out[c, :2, 3] = M, t
+    return out.astype(np.float32)
+
+
+def aug_b2(mod):
+    rng = np.random.default_rng(900)
+    cams = syn.make_cameras(2)
+    l2i = cams["lidar2image"].copy()
+    l2i[1, :, :3, :] *= rng.uniform(0.97, 1.03, size=(6, 1, 1)).astype(np.float32)     # other intrinsics in scene 1 (x, y, depth rows alike)
+    l2i[1, :, :2, :] *= np.float32(1.02)
+    lidar_aug = np.repeat(np.eye(4, dtype=np.float32)[None], 2, 0)
+    a, sc = -0.3, 1.04                                                                   # rotation, scaling, translation: not orthogonal
+    lidar_aug[1, :3, :3] = sc * np.array([[np.cos(a), -np.sin(a), 0], [np.sin(a), np.cos(a), 0], [0, 0, 1]])
+    lidar_aug[1, :3, 3] = [0.4, -0.6, 0.15]
+    img_aug = np.stack([img_aug_256x704(rng), img_aug_256x704(rng)], 0)
+    boxes, labels = [], []
+    for b in range(2):
+        _, bx, cls = syn.make_scene(3 + b, return_boxes=True)
+        bx = bx.astype(np.float32)
+        bx[:, :2] *= np.float32(0.6)               # nearer: at 256 x 704 far boxes fall under the 64 px minimum
+        if b == 1:
+            bx = bx[:16]
+            bx[:, :3] = bx[:, :3] @ lidar_aug[1, :3, :3].T + lidar_aug[1, :3, 3]
+            bx[:, 3:6] *= np.float32(sc)
+            bx[:, 6] += np.float32(a)
+            cls = cls[:16]
+        boxes.append(bx)
+        labels.append(cls.astype(np.int64) + 1)
+    rec = {"proj": {}, "probs": [], "probs_mean": [], "crop_rect": [], "crop_pair": []}
+    head = make_head(mod, [256, 704], rec)
+    images = np.stack([procedural_images(256, 704), procedural_images(256, 704)[::-1].copy()], 0)   # scene 1: the cameras' images in reverse
+    bd = {"batch_size": 2, "camera_imgs": torch.from_numpy(images), "camera_intrinsics": torch.from_numpy(cams["camera_intrinsics"]),
+          "camera2lidar": torch.from_numpy(cams["camera2lidar"]), "img_aug_matrix": torch.from_numpy(img_aug),
+          "lidar_aug_matrix": torch.from_numpy(lidar_aug), "lidar2image": torch.from_numpy(l2i)}
+    pd = [{"pred_boxes": torch.from_numpy(boxes[b]), "pred_labels": torch.from_numpy(labels[b]), "pred_scores": torch.zeros(boxes[b].shape[0])}
+          for b in range(2)]
+    seen_at, n_probs = [0], [0]
+    plain_project = head.project_to_camera
+
+    def project_mark(batch_dict, points, batch_idx=0, cam_idx=0):      # where scene 1's crops begin in the encoder's record
+        if batch_idx == 1 and len(seen_at) == 1:
+            seen_at.append(sum(p.shape[0] for p in head.clip.seen))
+        return plain_project(batch_dict, points, batch_idx, cam_idx)
+    head.project_to_camera = project_mark
+    run_forward(head, bd, pd, rec, keep_crops=False)    # (keep_crops=True only works for one scene: :370-372 turn the lists into tensors)
+    pooled = np.concatenate(head.clip.seen, 0).astype(np.float32)
+    if len(seen_at) == 1:
+        seen_at.append(pooled.shape[0])
+    out = os.path.join(HERE, "clipcrop_aug_b2.npz")
+    data = {"lidar_aug": lidar_aug, "img_aug": img_aug, "lidar2image": l2i, "pooled": pooled, "probs": np.concatenate(rec["probs"], 0),
+            "crop_pair": np.array(rec["crop_pair"], np.int32).reshape(-1, 2), "crop_rect": np.array(rec["crop_rect"], np.int32).reshape(-1, 3),
+            "crops_per_scene": np.array([seen_at[1], pooled.shape[0] - seen_at[1]], np.int64)}
+    for b in range(2):
+        data.update({f"boxes{b}": boxes[b], f"orig_labels{b}": pd[b]["orig_labels"].numpy(), f"pred_labels{b}": pd[b]["pred_labels"].numpy(),
+                     f"pred_scores{b}": pd[b]["pred_scores"].float().numpy(), f"probs_mean{b}": rec["probs_mean"][b],
+                     f"proj_yxz{b}": proj_array(rec, b, boxes[b].shape[0])})
+    np.savez_compressed(out, **data)
+    print(out, "boxes", [x.shape[0] for x in boxes], "crops", data["crops_per_scene"].tolist(), "labels", [pd[b]["pred_labels"].tolist() for b in range(2)])
+
+
 def main():
     H.cpu_only_torch()
     H.load_reference()
@@ -64,17 +213,12 @@ def main():
     sys.modules["torchvision.utils"].save_image = lambda *a, **k: None
     sys.modules["torchvision.transforms"].ToPILImage = object
     mod = importlib.import_module("pcdet.models.dense_heads.clip_box_classification")
-    for seed in ([int(a) for a in sys.argv[1:]] or [0, 1, 2]):
-        head = object.__new__(mod.CLIPBoxClassification)
-        torch.nn.Module.__init__(head)
-        head.image_order = [2, 0, 1, 5, 3, 4]
-        head.image_size = [900, 1600]
-        head.all_class_names = ['car', 'truck', 'construction_vehicle', 'bus', 'trailer', 'barrier', 'motorcycle', 'bicycle',
-                                'pedestrian', 'traffic_cone']
-        head.clip = FakeClip()
-        head.text_features = text_features().half()
-        head.min_crop_size = 64
-        head.unif_grid = F.affine_grid(theta=torch.eye(2, 3).unsqueeze(0), size=[1, 3, 224, 224])
+    args = sys.argv[1:] or ["0", "1", "2", "aug_b2"]
+    if "aug_b2" in args:
+        aug_b2(mod)
+    for seed in [int(a) for a in args if a != "aug_b2"]:
+        rec = {"proj": {}, "probs": [], "probs_mean": [], "crop_rect": [], "crop_pair": []}
+        head = make_head(mod, [900, 1600], rec)
 
         _, boxes, cls = syn.make_scene(seed, return_boxes=True)
         rng = np.random.default_rng(500 + seed)
@@ -107,13 +251,15 @@ def main():
               "lidar_aug_matrix": torch.from_numpy(lidar_aug)[None], "lidar2image": torch.from_numpy(cams["lidar2image"])}
         pd = [{"pred_boxes": torch.from_numpy(boxes), "pred_labels": torch.from_numpy(cls.astype(np.int64) + 1),
                "pred_scores": torch.rand(boxes.shape[0])}]
-        head.forward(bd, pd, keep_crops=True)
+        run_forward(head, bd, pd, rec, keep_crops=True)
         pooled = np.concatenate(head.clip.seen, 0) if head.clip.seen else np.zeros((0, 192), np.float32)
         out = os.path.join(HERE, f"clipcrop_seed{seed}.npz")
         np.savez_compressed(out, boxes=boxes, lidar_aug=lidar_aug, img_aug=img_aug[0], lidar2image=cams["lidar2image"][0],
                             pooled=pooled.astype(np.float32), probs=head.crop_infos["logits"].float().numpy(),
                             pred_labels=pd[0]["pred_labels"].numpy(), pred_scores=pd[0]["pred_scores"].float().numpy(),
-                            orig_labels=pd[0]["orig_labels"].numpy())
+                            orig_labels=pd[0]["orig_labels"].numpy(), probs_mean=rec["probs_mean"][0],
+                            proj_yxz=proj_array(rec, 0, boxes.shape[0]), crop_pair=np.array(rec["crop_pair"], np.int32).reshape(-1, 2),
+                            crop_rect=np.array(rec["crop_rect"], np.int32).reshape(-1, 3))
         print(out, "boxes", boxes.shape[0], "crops", pooled.shape[0], "labels", pd[0]["pred_labels"].tolist())
 
 
