@@ -49,11 +49,13 @@ inline void att_geometry(long long n, int *split_len, int *tile_len) {
 
 // ---- (a) attention ---------------------------------------------------------------------------------------------------------
 
+// stats (NULL in fnp_tf_attention and in the decoder): the softmax statistics (M, L) per (scene, head, query) for the backward of
+// tfattn_grad.hip, written by whichever launch writes out; the arithmetic of out does not depend on it.
 template <int QB>
 __global__ __launch_bounds__(kAttThreads) void tf_attn_kernel(const float *__restrict__ q, const float *__restrict__ k,
                                                               const float *__restrict__ v, int Kq, int N, int split_len, int nsplit,
                                                               int nchunk, float *__restrict__ pacc, float *__restrict__ pml,
-                                                              float *__restrict__ out) {
+                                                              float *__restrict__ out, float *__restrict__ stats) {
     const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z / nchunk, chunk = blockIdx.z % nchunk;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
     const int nblk = (Kq + 15) >> 4;
@@ -146,6 +148,7 @@ __global__ __launch_bounds__(kAttThreads) void tf_attn_kernel(const float *__res
         if (nsplit == 1) {
             float4 o = make_float4(acc[t][0] / lt, acc[t][1] / lt, acc[t][2] / lt, acc[t][3] / lt);
             *reinterpret_cast<float4 *>(out + ((size_t)b * Kq + row) * kD + 16 * h + 4 * g) = o;
+            if (stats && g == 0) *reinterpret_cast<float2 *>(stats + (((size_t)b * kHeads + h) * Kq + row) * 2) = make_float2(m[t], lt);
         } else {
             const size_t slot = (((size_t)b * nsplit + split) * kHeads + h) * Kq + row;
             *reinterpret_cast<float4 *>(pacc + slot * 16 + 4 * g) = make_float4(acc[t][0], acc[t][1], acc[t][2], acc[t][3]);
@@ -154,9 +157,10 @@ __global__ __launch_bounds__(kAttThreads) void tf_attn_kernel(const float *__res
     }
 }
 
-// one thread per (scene, query, head, 4 dims): the partials of the splits in split order
+// one thread per (scene, query, head, 4 dims): the partials of the splits in split order; stats (or NULL) gets (M, L)
 __global__ __launch_bounds__(256) void tf_attn_merge_kernel(const float *__restrict__ pacc, const float *__restrict__ pml, int Kq,
-                                                            int nsplit, long long total, float *__restrict__ out) {
+                                                            int nsplit, long long total, float *__restrict__ out,
+                                                            float *__restrict__ stats) {
     const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
     if (e >= total) return;
     const int quad = (int)(e & 3), h = (int)((e >> 2) & 7);
@@ -174,6 +178,7 @@ __global__ __launch_bounds__(256) void tf_attn_merge_kernel(const float *__restr
         o0 = fmaf(a.x, w, o0), o1 = fmaf(a.y, w, o1), o2 = fmaf(a.z, w, o2), o3 = fmaf(a.w, w, o3);
     }
     *reinterpret_cast<float4 *>(out + (size_t)br * kD + 16 * h + 4 * quad) = make_float4(o0 / L, o1 / L, o2 / L, o3 / L);
+    if (stats && quad == 0) *reinterpret_cast<float2 *>(stats + (((size_t)b * kHeads + h) * Kq + row) * 2) = make_float2(M, L);
 }
 
 // ---- (b) key / value projection ----------------------------------------------------------------------------------------------
@@ -556,7 +561,8 @@ long long att_ws_floats(long long B, long long Kq, long long N) {
     return (B > 0 ? B : 1) * nsplit * kHeads * Kq * 18;
 }
 
-int launch_attention(const float *q, const float *k, const float *v, int B, int Kq, int N, float *ws, float *out, hipStream_t s) {
+int launch_attention(const float *q, const float *k, const float *v, int B, int Kq, int N, float *ws, float *out, hipStream_t s,
+                     float *stats = nullptr) {
     int sl, tl;
     att_geometry(N, &sl, &tl);
     // A workgroup takes 4 * QB blocks of 16 queries (wave w the blocks w, w + 4, ...).  Many keys: up to four blocks per wave, so
@@ -571,7 +577,7 @@ int launch_attention(const float *q, const float *k, const float *v, int B, int 
     const dim3 grid(nsplit, kHeads, B * nchunk);
 #define FNP_ATT(QB)                                                                                                              \
     hipLaunchKernelGGL(HIP_KERNEL_NAME(tf_attn_kernel<QB>), grid, dim3(kAttThreads), 0, s, q, k, v, Kq, N, sl, nsplit, nchunk, pacc, \
-                       pml, out)
+                       pml, out, stats)
     if (qb == 1) FNP_ATT(1);
     else if (qb == 2) FNP_ATT(2);
     else if (qb == 3) FNP_ATT(3);
@@ -581,7 +587,7 @@ int launch_attention(const float *q, const float *k, const float *v, int B, int 
     if (nsplit > 1) {
         const long long total = (long long)B * Kq * 32;
         hipLaunchKernelGGL(tf_attn_merge_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, (const float *)pacc,
-                           (const float *)pml, Kq, nsplit, total, out);
+                           (const float *)pml, Kq, nsplit, total, out, stats);
         FNP_LAUNCH_CHECK();
     }
     return FNP_OK;
@@ -619,6 +625,18 @@ extern "C" int fnp_tf_attention(const float *q, const float *k, const float *v, 
     const long long need = att_ws_floats(batch_size, num_queries, num_keys) * 4;
     if (need && (!workspace || workspace_bytes < need)) return FNP_ERR_WORKSPACE;
     return launch_attention(q, k, v, batch_size, num_queries, (int)num_keys, (float *)workspace, out, (hipStream_t)stream);
+}
+
+// the same launches with the softmax statistics (M, L) per (scene, head, query) written as well: what fnp_tf_attention_backward reads
+extern "C" int fnp_tf_attention_stats(const float *q, const float *k, const float *v, int batch_size, int num_queries, int64_t num_keys,
+                                      void *workspace, int64_t workspace_bytes, float *out, float *stats, fnp_stream_t stream) {
+    if (!att_shape_ok(batch_size, num_queries, num_keys)) return FNP_ERR_ARG;
+    if (batch_size == 0) return FNP_OK;
+    if (!q || !k || !v || !out || !stats) return FNP_ERR_ARG;
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)stats | (uintptr_t)workspace) & 15) return FNP_ERR_ARG;
+    const long long need = att_ws_floats(batch_size, num_queries, num_keys) * 4;
+    if (need && (!workspace || workspace_bytes < need)) return FNP_ERR_WORKSPACE;
+    return launch_attention(q, k, v, batch_size, num_queries, (int)num_keys, (float *)workspace, out, (hipStream_t)stream, stats);
 }
 
 extern "C" int64_t fnp_tf_decoder_workspace_bytes(int batch_size, int num_queries, int64_t num_keys, int ffn, int n_head_out) {

@@ -4,7 +4,9 @@ two position-embedding MLPs, three LayerNorms, the FFN) and SeparateHead_Transfu
 heads) are several dozen launches per scene in torch, with 8 x 200 x 32 400 scores written out and read back; here they are
 seven launches of csrc/tfdecoder.hip (eight with more than 256 queries) on one stream, with nothing read on the host.
 
-SeparateHead_Transfusion keeps the reference's names and init.  attention(q, k, v) is the attention kernel alone.
+SeparateHead_Transfusion keeps the reference's names and init.  attention(q, k, v) is the attention kernel alone;
+attention_autograd(q, k, v) is the same forward (bit for bit) with a backward on csrc/tfattn_grad.hip, which the decoder layer's
+opt-in fused_attention_grad route uses for its cross attention under autograd.
 DecoderHead(decoder, prediction_head)(query_feat, lidar_feat_flatten, query_pos, bev_pos) returns the reference's res_layer
 dict with `center` already offset.  Both DecoderHead and TransformerDecoderLayer.forward fall back to the modules called
 plainly whenever decoder_plain_reasons() / heads_plain_reasons() find something against the device path.
@@ -89,6 +91,86 @@ def attention(q, k, v, out=None):
     lib.check(L.fnp_tf_attention(lib.ptr(q), lib.ptr(k), lib.ptr(v), B, Kq, N, lib.ptr(ws), ws_bytes, lib.ptr(out), lib.stream()),
               "fnp_tf_attention")
     return out
+
+
+def attention_backward_geometry(n_keys):
+    """(key_block, wave_keys) of fnp_tf_attention_backward's key-stationary kernel: constants, 256 and 64"""
+    L = lib.load()
+    kb, wk = ctypes.c_int(), ctypes.c_int()
+    lib.check(L.fnp_tf_attention_backward_geometry(int(n_keys), ctypes.byref(kb), ctypes.byref(wk)), "fnp_tf_attention_backward_geometry")
+    return kb.value, wk.value
+
+
+def _workspace(L, fn, B, Kq, N, dev):
+    ws_bytes = getattr(L, fn)(B, Kq, N)
+    if ws_bytes < 0:
+        raise lib.FnpError(f"{fn}({B}, {Kq}, {N}) failed")
+    return (torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev) if ws_bytes else None), ws_bytes
+
+
+def attention_stats(q, k, v, out=None, stats=None):
+    """attention() that also returns the softmax statistics: -> out (B, Kq, 128), stats (B, 8, Kq, 2) holding (M, L) per scene,
+    head and query (include/fnp.h).  out has attention()'s bits.  No gradient; attention_autograd is the differentiable form."""
+    B, Kq, N = check_attention(q, k, v)
+    L = lib.load()
+    lib.require_device(q, k, v)
+    q, k, v = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
+    if out is None:
+        out = torch.empty((B, Kq, D_MODEL), dtype=torch.float32, device=q.device)
+    if stats is None:
+        stats = torch.empty((B, N_HEAD, Kq, 2), dtype=torch.float32, device=q.device)
+    assert out.shape == (B, Kq, D_MODEL) and out.dtype == torch.float32 and out.is_contiguous()
+    assert stats.shape == (B, N_HEAD, Kq, 2) and stats.dtype == torch.float32 and stats.is_contiguous()
+    if B:
+        ws, ws_bytes = _workspace(L, "fnp_tf_attention_workspace_bytes", B, Kq, N, q.device)
+        lib.check(L.fnp_tf_attention_stats(lib.ptr(q), lib.ptr(k), lib.ptr(v), B, Kq, N, lib.ptr(ws), ws_bytes, lib.ptr(out),
+                                           lib.ptr(stats), lib.stream()), "fnp_tf_attention_stats")
+    return out, stats
+
+
+def attention_backward(q, k, v, out, stats, d_out, dq=None, dk=None, dv=None):
+    """fnp_tf_attention_backward on contiguous f32 device tensors: writes the gradients into whichever of dq (B, Kq, 128), dk
+    and dv (B, N, 128) are given and skips the others; out and stats as attention_stats returned them"""
+    B, Kq, N = check_attention(q, k, v)
+    L = lib.load()
+    lib.require_device(q, k, v, out, stats, d_out, dq, dk, dv)
+    assert out.shape == q.shape and d_out.shape == q.shape and stats.shape == (B, N_HEAD, Kq, 2)
+    for t, like in ((dq, q), (dk, k), (dv, v)):
+        assert t is None or (t.shape == like.shape and t.dtype == torch.float32)
+    assert all(t.dtype == torch.float32 for t in (out, stats, d_out))
+    if B and (dq is not None or dk is not None or dv is not None):
+        ws, ws_bytes = _workspace(L, "fnp_tf_attention_backward_workspace_bytes", B, Kq, N, q.device)
+        lib.check(L.fnp_tf_attention_backward(lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(out), lib.ptr(stats), lib.ptr(d_out), B, Kq, N,
+                                              lib.ptr(ws), ws_bytes, lib.ptr(dq), lib.ptr(dk), lib.ptr(dv), lib.stream()),
+                  "fnp_tf_attention_backward")
+    return dq, dk, dv
+
+
+class _AttentionGrad(torch.autograd.Function):
+    """attention_stats forward, attention_backward (csrc/tfattn_grad.hip) backward.  Saved for the backward: q, k, v, out and
+    the (M, L) statistics (B, 8, Kq, 2); nothing with Kq x N elements exists at any time."""
+
+    @staticmethod
+    def forward(ctx, q, k, v):
+        q, k, v = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
+        out, stats = attention_stats(q, k, v)
+        ctx.save_for_backward(q, k, v, out, stats)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, d_out):
+        q, k, v, out, stats = ctx.saved_tensors
+        grads = [torch.empty_like(t) if need else None for t, need in zip((q, k, v), ctx.needs_input_grad)]
+        attention_backward(q, k, v, out, stats, d_out.contiguous(), *grads)
+        return tuple(grads)
+
+
+def attention_autograd(q, k, v):
+    """attention(q, k, v) under autograd: the same values bit for bit, and gradients for whichever of q, k, v require them
+    (dq, dk, dv of softmax(0.25 q.k) v; the scores are recomputed tile by tile, never stored).  A second derivative raises."""
+    check_attention(q, k, v)
+    return _AttentionGrad.apply(q, k, v)
 
 
 # ---- path selection ----------------------------------------------------------------------------------------------------------

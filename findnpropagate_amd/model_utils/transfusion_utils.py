@@ -4,7 +4,8 @@ reference checkpoint's `decoder.*` keys load with strict=True.
 
 TransformerDecoderLayer.forward runs on the library's kernels (csrc/tfdecoder.hip, seven launches, eight with more than 256 queries, nothing read on the host)
 when plain_reasons() finds nothing against it; otherwise it is forward_plain, the reference's own torch ops with dropout and
-gradients, so training is unchanged."""
+gradients, so training is unchanged.  With the attribute fused_attention_grad set (default off) the cross attention's core runs
+on the library's differentiable kernels there (forward_fused_grad) whenever fused_grad_reasons() finds nothing against it."""
 import torch
 import torch.nn.functional as F
 from torch import nn
@@ -84,13 +85,69 @@ class TransformerDecoderLayer(nn.Module):
             self._device_pack = DevicePack(self, None)
         return self._device_pack.reasons(query, key, query_pos, key_pos, key_padding_mask, attn_mask)
 
+    # Opt-in: under autograd or in train(), where the eval device path does not apply, run the cross attention's core
+    # softmax(0.25 q.k) v on the library's differentiable kernels (dense_heads.transfusion_decoder.attention_autograd) instead
+    # of materialising the 8 x Pq x Pk scores.  A plain attribute: not a constructor argument, not in the state_dict.
+    fused_attention_grad = False
+
+    def fused_grad_reasons(self, query, key, query_pos, key_pos, key_padding_mask=None, attn_mask=None):
+        """what stands against forward_fused_grad, as a list of short strings (empty: it can run).  Attention dropout is not in
+        the kernels: a layer in train() with multihead_attn.dropout > 0 keeps forward_plain."""
+        from ..dense_heads.transfusion_decoder import D_MODEL, MAX_QUERIES, N_HEAD
+
+        r = []
+        if key_padding_mask is not None or attn_mask is not None:
+            r.append("mask")
+        mha = self.multihead_attn
+        if mha.embed_dim != D_MODEL or mha.num_heads != N_HEAD or mha.in_proj_weight is None or mha.in_proj_bias is None:
+            r.append("d_model / nhead")
+        if self.training and mha.dropout != 0:
+            r.append("attention dropout")
+        tensors = [query, key, query_pos, key_pos] + list(self.parameters()) + [b for b in self.buffers() if b.is_floating_point()]
+        if any(t.dtype != torch.float32 for t in tensors):
+            r.append("dtype")
+        if not all(t.is_cuda for t in tensors) or len({t.device for t in tensors}) > 1:
+            r.append("not on the device")
+        if not r:
+            ok = query.dim() == 3 and key.dim() == 3 and query.shape[1] == D_MODEL and key.shape[:2] == (query.shape[0], D_MODEL)
+            if not (ok and 1 <= query.shape[2] <= MAX_QUERIES and 1 <= key.shape[2] < 2 ** 31 // D_MODEL):
+                r.append("shape")
+        return r
+
     def forward(self, query, key, query_pos, key_pos, key_padding_mask=None, attn_mask=None):
-        if self.plain_reasons(query, key, query_pos, key_pos, key_padding_mask, attn_mask):
+        reasons = self.plain_reasons(query, key, query_pos, key_pos, key_padding_mask, attn_mask)
+        if reasons:
+            wanted = self.fused_attention_grad and ("autograd" in reasons or "training mode" in reasons)
+            if wanted and not self.fused_grad_reasons(query, key, query_pos, key_pos, key_padding_mask, attn_mask):
+                return self.forward_fused_grad(query, key, query_pos, key_pos)
             return self.forward_plain(query, key, query_pos, key_pos, key_padding_mask, attn_mask)
         return self._device_pack.run(query, key, query_pos, key_pos)[0]
 
     def forward_plain(self, query, key, query_pos, key_pos, key_padding_mask=None, attn_mask=None):
         """the layer as torch ops, differentiable, with dropout in train(): what forward runs off the device path"""
+        return self._forward_torch(query, key, query_pos, key_pos, key_padding_mask, attn_mask, self._cross_plain)
+
+    def forward_fused_grad(self, query, key, query_pos, key_pos):
+        """forward_plain with the cross attention's core on the differentiable kernels: the in- and out-projections stay
+        F.linear, everything else the same torch ops in the same order.  No masks, no attention dropout (fused_grad_reasons)."""
+        return self._forward_torch(query, key, query_pos, key_pos, None, None, self._cross_fused)
+
+    def _cross_plain(self, q_in, m, key_padding_mask, attn_mask):
+        return self.multihead_attn(query=q_in, key=m, value=m, key_padding_mask=key_padding_mask, attn_mask=attn_mask)[0]
+
+    def _cross_fused(self, q_in, m, key_padding_mask, attn_mask):
+        """nn.MultiheadAttention(q_in (Pq, B, C), m, m)[0] without masks and dropout, on (B, L, 128) rows"""
+        from ..dense_heads.transfusion_decoder import attention_autograd
+
+        mha = self.multihead_attn
+        w, b, d = mha.in_proj_weight, mha.in_proj_bias, mha.embed_dim
+        rows_q, rows_m = q_in.transpose(0, 1), m.transpose(0, 1)
+        q = F.linear(rows_q, w[:d], b[:d])
+        k = F.linear(rows_m, w[d:2 * d], b[d:2 * d])
+        v = F.linear(rows_m, w[2 * d:], b[2 * d:])
+        return F.linear(attention_autograd(q, k, v), mha.out_proj.weight, mha.out_proj.bias).transpose(0, 1)
+
+    def _forward_torch(self, query, key, query_pos, key_pos, key_padding_mask, attn_mask, cross):
         q_pe = None if self.self_posembed is None else _rows(self.self_posembed(query_pos))
         k_pe = None if self.cross_posembed is None else _rows(self.cross_posembed(key_pos))
         x, memory = _rows(query), _rows(key)
@@ -98,8 +155,7 @@ class TransformerDecoderLayer(nn.Module):
             a = self.with_pos_embed(x, q_pe)
             x = self.norm1(x + self.dropout1(self.self_attn(a, a, value=a)[0]))
         m = self.with_pos_embed(memory, k_pe)
-        attended = self.multihead_attn(query=self.with_pos_embed(x, q_pe), key=m, value=m, key_padding_mask=key_padding_mask,
-                                       attn_mask=attn_mask)[0]
+        attended = cross(self.with_pos_embed(x, q_pe), m, key_padding_mask, attn_mask)
         x = self.norm2(x + self.dropout2(attended))
         x = self.norm3(x + self.dropout3(self.linear2(self.dropout(self.activation(self.linear1(x))))))
         return x.permute(1, 2, 0)

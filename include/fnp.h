@@ -968,6 +968,42 @@ int fnp_tf_decoder(const float *query_feat, const float *lidar_feat, const float
                    int n_heads, const int *head_out, int center_head, void *workspace, int64_t workspace_bytes,
                    float *out_query_feat, float *out_heads, fnp_stream_t stream);
 
+/* The attention core softmax(0.25 q . k^T) v as a differentiable operator (additive, ABI 14; the forward's statistics come from
+ * the kernels of csrc/tfdecoder.hip, the backward is csrc/tfattn_grad.hip).  Conventions and shapes are those of fnp_tf_attention:
+ * f32, every product on the f32 MFMA, no atomics, a stream, no allocation, no synchronisation, bit-identical from run to run, a
+ * scene's results independent of the batch around it, 16-byte aligned pointers.  The score matrix is never stored: the backward
+ * recomputes it tile by tile with the forward's arithmetic (q scaled by 0.25 first, the same k-ordered chain per score).
+ *
+ * fnp_tf_attention_stats: fnp_tf_attention (same kernels, same workspace, `out` bit for bit) that also writes
+ * stats (B, 8, Kq, 2): per (scene, head, query) the pair (M, L), M = the maximum score, L = sum_j exp(s_j - M) as the forward
+ * summed it (with several splits: the merge's M and L).  The pair and not the log-sum-exp: s - M is exact near the maximum and
+ * 1 / L carries one rounding, whereas an f32 log-sum-exp of magnitude 11 (N = 32 400) alone is half an ulp = 5e-7 off, a
+ * relative error common to a query's whole row of probabilities.
+ *
+ * fnp_tf_attention_backward: with P_ij = exp(s_ij - M_i) * (1 / L_i), D_i = sum_d dO_id O_id (per head), dP_ij = dO_i . v_j and
+ * dS_ij = P_ij (dP_ij - D_i):  dV_j = sum_i P_ij dO_i,  dK_j = 0.25 sum_i dS_ij q_i,  dQ_i = 0.25 sum_j dS_ij k_j.
+ * q, out, d_out, dq (B, Kq, 128); k, v, dk, dv (B, N, 128); stats as above; all contiguous.  Any of dq, dk, dv may be NULL: that
+ * result is not written, and its kernel (dq) or its products (dk, dv) are skipped.
+ *   1. Prologue: D_i per (scene, head, query) into the workspace, the diagonal of dO O^T on the MFMA.
+ *   2. dK and dV, key-stationary (fnp_tf_attention_backward_geometry, constants: key_block = 256, wave_keys = 64): one workgroup
+ *      per (block of key_block keys, head, scene), wave w of its four owns the wave_keys keys from key_block * block +
+ *      wave_keys * w as four MFMA column blocks of 16, walks ALL queries in blocks of 16 in ascending order and keeps the dK and
+ *      dV rows of its keys in registers: every row has one owner, so there is no reduction across workgroups.  Query rows past Kq
+ *      enter with P = 0.
+ *   3. dQ, query-stationary, on the forward's geometry (fnp_tf_attention_geometry; the same splits, tiles and query chunks): one
+ *      workgroup per (split, head, scene x query chunk) accumulates its split's part of dQ over tiles of 64 keys in ascending
+ *      order; with several splits the parts go to the workspace and a second launch adds them in split order.  The factor 0.25
+ *      is applied last.
+ * workspace: fnp_tf_attention_backward_workspace_bytes(B, Kq, N) bytes (D, and with several splits the dQ parts: 16 floats per
+ * (scene, split, head, query); negative: the shape is out of contract).  It does not depend on which results are asked for. */
+int fnp_tf_attention_stats(const float *q, const float *k, const float *v, int batch_size, int num_queries, int64_t num_keys,
+                           void *workspace, int64_t workspace_bytes, float *out, float *stats, fnp_stream_t stream);
+int fnp_tf_attention_backward_geometry(int64_t n_keys, int *key_block, int *wave_keys);
+int64_t fnp_tf_attention_backward_workspace_bytes(int batch_size, int num_queries, int64_t num_keys);
+int fnp_tf_attention_backward(const float *q, const float *k, const float *v, const float *out, const float *stats,
+                              const float *d_out, int batch_size, int num_queries, int64_t num_keys, void *workspace,
+                              int64_t workspace_bytes, float *dq, float *dk, float *dv, fnp_stream_t stream);
+
 /* Hungarian assignment and per-query targets of TransFusionHead (transfusion_head.py:352-444, hungarian_assigner.py:61-132;
  * additive, ABI 14; csrc/tfassign.hip).  The batch goes in four launches (valid rows, cost, match, targets); every device call
  * takes a stream, allocates nothing, calls no synchronising HIP function and uses no atomics: results are bit-identical from
