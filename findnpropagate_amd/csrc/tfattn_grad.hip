@@ -19,6 +19,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "tfattn_dropout.h"
 
 namespace {
 
@@ -32,6 +33,16 @@ constexpr int kWaveKeys = 64;      // keys a wave of the key-stationary kernel o
 constexpr int kKeyBlock = 256;     // keys per workgroup of the key-stationary kernel: four waves
 
 #define MFMA(a, b, c) __builtin_amdgcn_mfma_f32_16x16x4f32((a), (b), (c), 0, 0, 0)
+
+// x of lane `from` (0..3) of this lane's quad: a DPP quad permute, every lane of the wave active
+__device__ __forceinline__ uint32_t quad_lane(uint32_t x, int from) {
+    switch (from) {
+        case 0: return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x00, 0xf, 0xf, false);
+        case 1: return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0x55, 0xf, 0xf, false);
+        case 2: return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xaa, 0xf, 0xf, false);
+        default: return (uint32_t)__builtin_amdgcn_mov_dpp((int)x, 0xff, 0xf, 0xf, false);
+    }
+}
 
 // ---- D_i = dO_i . O_i per head: the diagonal of dO O^T, one wave per (16 queries, head, scene) -------------------------------
 
@@ -55,15 +66,24 @@ __global__ __launch_bounds__(64) void tf_attn_bwd_d_kernel(const float *__restri
 
 // ---- dK and dV, key-stationary ------------------------------------------------------------------------------------------------
 
-template <bool WANT_DK, bool WANT_DV>
+// DROP is empty (fnp_tf_attention_backward: the kernel and its arguments as they always were) or one fnp_dropout_args: then
+// dV sums dO (P Z) and dS = P (Z dP - D), Z = keep / (1 - p_eff) (tfattn_dropout.h).  A lane holds four QUERIES 4g + r against one
+// key, but a generator call serves four KEYS of one query: lane i calls for (query 4g + (i & 3), the aligned key group of key i)
+// and keeps the four bits; the lanes of a quad share that key group, so the bit of (query 4g + r, key i) is bit i & 3 of quad
+// lane r's word, fetched by a quad broadcast.  (Four calls per lane instead: 184 us against 130 us for dK and dV at one scene)
+template <bool WANT_DK, bool WANT_DV, typename... DROP>
 __global__ __launch_bounds__(kThreads) void tf_attn_bwd_kv_kernel(const float *__restrict__ q, const float *__restrict__ k,
                                                                   const float *__restrict__ v, const float *__restrict__ d_out,
                                                                   const float *__restrict__ stats, const float *__restrict__ dsum,
-                                                                  int Kq, int N, float *__restrict__ dk, float *__restrict__ dv) {
+                                                                  int Kq, int N, float *__restrict__ dk, float *__restrict__ dv,
+                                                                  DROP... drop) {
     const int h = blockIdx.y, b = blockIdx.z;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
     const int key0 = blockIdx.x * kKeyBlock + wave * kWaveKeys;
     if (key0 >= N) return;                                 // wave-uniform; the kernel has no barrier
+    constexpr bool kDrop = sizeof...(DROP) != 0;
+    const fnp_dropout_args da = fnp_dropout_of(drop...);
+    const unsigned long long seed = kDrop ? *da.seed : 0ull;
     const float *qs = q + (size_t)b * Kq * kD + 16 * h;
     const float *dos = d_out + (size_t)b * Kq * kD + 16 * h;
     const float *st = stats + ((size_t)b * kHeads + h) * Kq * 2;
@@ -106,11 +126,19 @@ __global__ __launch_bounds__(kThreads) void tf_attn_bwd_kv_kernel(const float *_
             dp = MFMA(dof.y, vf[c].y, dp);
             dp = MFMA(dof.z, vf[c].z, dp);
             dp = MFMA(dof.w, vf[c].w, dp);
+            uint32_t mine = 0;                             // the mask indexes nothing: a row past Kq or a key past N is a value like any
+            if (kDrop) mine = fnp_dropout_keep4(seed, da.threshold, b, h, blk * 16 + 4 * g + (i & 3), (key0 + 16 * c + i) >> 2);
 #pragma unroll
             for (int r = 0; r < 4; ++r) {
                 const float p = expf(s[r] - m[r]) * inv_l[r];
-                if (WANT_DV) accv[c] = MFMA(docol[r], p, accv[c]);
-                if (WANT_DK) acck[c] = MFMA(qcol[r], p * (dp[r] - dd[r]), acck[c]);
+                if (kDrop) {
+                    const float z = (quad_lane(mine, r) >> (i & 3)) & 1 ? da.scale : 0.f;
+                    if (WANT_DV) accv[c] = MFMA(docol[r], p * z, accv[c]);
+                    if (WANT_DK) acck[c] = MFMA(qcol[r], p * (z * dp[r] - dd[r]), acck[c]);
+                } else {
+                    if (WANT_DV) accv[c] = MFMA(docol[r], p, accv[c]);
+                    if (WANT_DK) acck[c] = MFMA(qcol[r], p * (dp[r] - dd[r]), acck[c]);
+                }
             }
         }
     }
@@ -126,15 +154,20 @@ __global__ __launch_bounds__(kThreads) void tf_attn_bwd_kv_kernel(const float *_
 
 // ---- dQ, query-stationary on the forward's splits ------------------------------------------------------------------------------
 
-template <int QB>
+// DROP as in the key-stationary kernel: dS = P (Z dP - D).  In the forward's orientation a lane's four keys of a query are one
+// aligned group of four, one generator call, as in tf_attn_kernel.
+template <int QB, typename... DROP>
 __global__ __launch_bounds__(kThreads) void tf_attn_bwd_q_kernel(const float *__restrict__ q, const float *__restrict__ k,
                                                                  const float *__restrict__ v, const float *__restrict__ d_out,
                                                                  const float *__restrict__ stats, const float *__restrict__ dsum,
                                                                  int Kq, int N, int split_len, int nsplit, int nchunk,
-                                                                 float *__restrict__ part, float *__restrict__ dq) {
+                                                                 float *__restrict__ part, float *__restrict__ dq, DROP... drop) {
     const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z / nchunk, chunk = blockIdx.z % nchunk;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
     const int nblk = (Kq + 15) >> 4;
+    constexpr bool kDrop = sizeof...(DROP) != 0;
+    const fnp_dropout_args da = fnp_dropout_of(drop...);
+    const unsigned long long seed = kDrop ? *da.seed : 0ull;
     const float *qs = q + (size_t)b * Kq * kD + 16 * h;
     const float *dos = d_out + (size_t)b * Kq * kD + 16 * h;
     const float *ks = k + (size_t)b * N * kD + 16 * h;
@@ -194,11 +227,14 @@ __global__ __launch_bounds__(kThreads) void tf_attn_bwd_q_kernel(const float *__
                 dp = MFMA(vf[kb].y, dof[t].y, dp);
                 dp = MFMA(vf[kb].z, dof[t].z, dp);
                 dp = MFMA(vf[kb].w, dof[t].w, dp);
+                uint32_t keep = 0;                         // the mask indexes nothing: a row past Kq or a key past N is a value like any
+                if (kDrop) keep = fnp_dropout_keep4(seed, da.threshold, b, h, (chunk * (4 * QB) + t * 4 + wave) * 16 + i, (n0 + 16 * kb + 4 * g) >> 2);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     float p = expf(s[r] - m[t]) * inv_l[t];
                     if (n0 + 16 * kb + 4 * g + r >= n_end) p = 0.f;
-                    o = MFMA(kcol[kb][r], p * (dp[r] - dd[t]), o);
+                    if (kDrop) o = MFMA(kcol[kb][r], p * (((keep >> r) & 1 ? da.scale : 0.f) * dp[r] - dd[t]), o);
+                    else o = MFMA(kcol[kb][r], p * (dp[r] - dd[t]), o);
                 }
             }
             acc[t] = o;
@@ -237,6 +273,19 @@ __global__ __launch_bounds__(256) void tf_attn_bwd_q_merge_kernel(const float *_
     *reinterpret_cast<float4 *>(dq + (size_t)br * kD + 16 * h + 4 * quad) = make_float4(0.25f * o0, 0.25f * o1, 0.25f * o2, 0.25f * o3);
 }
 
+// ---- the mask written out: one thread per (scene x head, query, aligned group of four keys) -------------------------------------
+
+__global__ __launch_bounds__(256) void tf_attn_dropout_mask_kernel(const unsigned long long *__restrict__ seed, uint32_t threshold, int Kq,
+                                                                   int N, uint8_t *__restrict__ keep) {
+    const int group = blockIdx.x * 256 + threadIdx.x, query = blockIdx.y, b = blockIdx.z >> 3, h = blockIdx.z & 7;
+    if (4ll * group >= N) return;
+    const uint32_t bits = fnp_dropout_keep4(*seed, threshold, b, h, query, group);
+    uint8_t *row = keep + ((size_t)blockIdx.z * Kq + query) * N;
+#pragma unroll
+    for (int r = 0; r < 4; ++r)
+        if (4 * group + r < N) row[4 * group + r] = (bits >> r) & 1;
+}
+
 // ---- host ------------------------------------------------------------------------------------------------------------------------
 
 bool shape_ok(long long B, long long Kq, long long N) {      // fnp_tf_attention's
@@ -267,9 +316,13 @@ extern "C" int64_t fnp_tf_attention_backward_workspace_bytes(int batch_size, int
     return ws_floats(batch_size, num_queries, num_keys) * 4;
 }
 
-extern "C" int fnp_tf_attention_backward(const float *q, const float *k, const float *v, const float *out, const float *stats,
-                                         const float *d_out, int batch_size, int num_queries, int64_t num_keys, void *workspace,
-                                         int64_t workspace_bytes, float *dq, float *dk, float *dv, fnp_stream_t stream) {
+namespace {
+
+// DROP: empty, or the one fnp_dropout_args every gradient kernel of the call gets
+template <typename... DROP>
+int launch_backward(const float *q, const float *k, const float *v, const float *out, const float *stats, const float *d_out,
+                    int batch_size, int num_queries, int64_t num_keys, void *workspace, int64_t workspace_bytes, float *dq, float *dk,
+                    float *dv, fnp_stream_t stream, DROP... drop) {
     if (!shape_ok(batch_size, num_queries, num_keys)) return FNP_ERR_ARG;
     if (batch_size == 0) return FNP_OK;
     if (!q || !k || !v || !out || !stats || !d_out) return FNP_ERR_ARG;
@@ -287,8 +340,8 @@ extern "C" int fnp_tf_attention_backward(const float *q, const float *k, const f
     if (dk || dv) {
         const dim3 grid((N + kKeyBlock - 1) / kKeyBlock, kHeads, B);
 #define FNP_KV(WK, WV)                                                                                                            \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(tf_attn_bwd_kv_kernel<WK, WV>), grid, dim3(kThreads), 0, s, q, k, v, d_out, stats,         \
-                       (const float *)dsum, Kq, N, dk, dv)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(tf_attn_bwd_kv_kernel<WK, WV, DROP...>), grid, dim3(kThreads), 0, s, q, k, v, d_out, stats, \
+                       (const float *)dsum, Kq, N, dk, dv, drop...)
         if (dk && dv) FNP_KV(true, true);
         else if (dk) FNP_KV(true, false);
         else FNP_KV(false, true);
@@ -305,8 +358,8 @@ extern "C" int fnp_tf_attention_backward(const float *q, const float *k, const f
         const int nchunk = (nblk + 4 * qb - 1) / (4 * qb);
         const dim3 grid(nsplit, kHeads, B * nchunk);
 #define FNP_Q(QB)                                                                                                                 \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(tf_attn_bwd_q_kernel<QB>), grid, dim3(kThreads), 0, s, q, k, v, d_out, stats,              \
-                       (const float *)dsum, Kq, N, sl, nsplit, nchunk, part, dq)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(tf_attn_bwd_q_kernel<QB, DROP...>), grid, dim3(kThreads), 0, s, q, k, v, d_out, stats,     \
+                       (const float *)dsum, Kq, N, sl, nsplit, nchunk, part, dq, drop...)
         if (qb == 1) FNP_Q(1);
         else if (qb == 2) FNP_Q(2);
         else if (qb == 3) FNP_Q(3);
@@ -320,5 +373,38 @@ extern "C" int fnp_tf_attention_backward(const float *q, const float *k, const f
             FNP_LAUNCH_CHECK();
         }
     }
+    return FNP_OK;
+}
+
+}  // namespace
+
+extern "C" int fnp_tf_attention_backward(const float *q, const float *k, const float *v, const float *out, const float *stats,
+                                         const float *d_out, int batch_size, int num_queries, int64_t num_keys, void *workspace,
+                                         int64_t workspace_bytes, float *dq, float *dk, float *dv, fnp_stream_t stream) {
+    return launch_backward(q, k, v, out, stats, d_out, batch_size, num_queries, num_keys, workspace, workspace_bytes, dq, dk, dv, stream);
+}
+
+// the same launches on the dropout instantiations of the two gradient kernels; out is the dropped output, so the prologue's D holds
+extern "C" int fnp_tf_attention_dropout_backward(const float *q, const float *k, const float *v, const float *out, const float *stats,
+                                                 const float *d_out, int batch_size, int num_queries, int64_t num_keys, void *workspace,
+                                                 int64_t workspace_bytes, float *dq, float *dk, float *dv, float p, const uint64_t *seed,
+                                                 fnp_stream_t stream) {
+    if (!(p >= 0.f && p < 1.f)) return FNP_ERR_ARG;
+    if (batch_size > 0 && (!seed || ((uintptr_t)seed & 7))) return FNP_ERR_ARG;
+    const uint32_t threshold = fnp_dropout_threshold(p);
+    return launch_backward(q, k, v, out, stats, d_out, batch_size, num_queries, num_keys, workspace, workspace_bytes, dq, dk, dv, stream,
+                           fnp_dropout_args{(const unsigned long long *)seed, threshold, fnp_dropout_scale(threshold)});
+}
+
+// keep (B, 8, Kq, N), one byte per element: what the three kernels derive, written out for the tests; no training path launches it
+extern "C" int fnp_tf_attention_dropout_mask(const uint64_t *seed, float p, int batch_size, int num_queries, int64_t num_keys,
+                                             uint8_t *keep, fnp_stream_t stream) {
+    if (!shape_ok(batch_size, num_queries, num_keys) || !(p >= 0.f && p < 1.f)) return FNP_ERR_ARG;
+    if (batch_size == 0) return FNP_OK;
+    if (!seed || ((uintptr_t)seed & 7) || !keep || (long long)batch_size * kHeads > 65535) return FNP_ERR_ARG;
+    const int N = (int)num_keys, groups = (N + 3) / 4;
+    hipLaunchKernelGGL(tf_attn_dropout_mask_kernel, dim3((groups + 255) / 256, num_queries, batch_size * kHeads), dim3(256), 0,
+                       (hipStream_t)stream, (const unsigned long long *)seed, fnp_dropout_threshold(p), num_queries, N, keep);
+    FNP_LAUNCH_CHECK();
     return FNP_OK;
 }

@@ -17,6 +17,7 @@
 #include <math.h>
 
 #include "common.h"
+#include "tfattn_dropout.h"
 
 namespace {
 
@@ -51,17 +52,23 @@ inline void att_geometry(long long n, int *split_len, int *tile_len) {
 
 // stats (NULL in fnp_tf_attention and in the decoder): the softmax statistics (M, L) per (scene, head, query) for the backward of
 // tfattn_grad.hip, written by whichever launch writes out; the arithmetic of out does not depend on it.
-template <int QB>
+// DROP is empty (every launch but fnp_tf_attention_dropout_stats': the kernel and its arguments as they always were) or one
+// fnp_dropout_args: then p feeds the V product as p * Z, Z = keep / (1 - p_eff) (tfattn_dropout.h), and l still sums every p.  A
+// lane's four keys n0 + 16 kb + 4 g + r of a query are one aligned group of four: one generator call.
+template <int QB, typename... DROP>
 __global__ __launch_bounds__(kAttThreads) void tf_attn_kernel(const float *__restrict__ q, const float *__restrict__ k,
                                                               const float *__restrict__ v, int Kq, int N, int split_len, int nsplit,
                                                               int nchunk, float *__restrict__ pacc, float *__restrict__ pml,
-                                                              float *__restrict__ out, float *__restrict__ stats) {
+                                                              float *__restrict__ out, float *__restrict__ stats, DROP... drop) {
     const int split = blockIdx.x, h = blockIdx.y, b = blockIdx.z / nchunk, chunk = blockIdx.z % nchunk;
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, i = lane & 15, g = lane >> 4;
     const int nblk = (Kq + 15) >> 4;
     const float *qs = q + (size_t)b * Kq * kD + 16 * h;
     const float *ks = k + (size_t)b * N * kD + 16 * h;
     const float *vs = v + (size_t)b * N * kD + 16 * h;
+    constexpr bool kDrop = sizeof...(DROP) != 0;
+    const fnp_dropout_args da = fnp_dropout_of(drop...);
+    const unsigned long long seed = kDrop ? *da.seed : 0ull;
 
     float4 qf[QB];
     f32x4 acc[QB];
@@ -126,13 +133,16 @@ __global__ __launch_bounds__(kAttThreads) void tf_attn_kernel(const float *__res
 #pragma unroll
             for (int r = 0; r < 4; ++r) o[r] *= sc;
 #pragma unroll
-            for (int kb = 0; kb < 4; ++kb)
+            for (int kb = 0; kb < 4; ++kb) {
+                uint32_t keep = 0;                         // the mask indexes nothing: a row past Kq or a key past N is a value like any
+                if (kDrop) keep = fnp_dropout_keep4(seed, da.threshold, b, h, (chunk * (4 * QB) + t * 4 + wave) * 16 + i, (n0 + 16 * kb + 4 * g) >> 2);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float p = expf(s[kb][r] - m_new);
                     psum += p;
-                    o = MFMA(vf[kb][r], p, o);
+                    o = MFMA(vf[kb][r], kDrop ? ((keep >> r) & 1 ? p * da.scale : 0.f) : p, o);
                 }
+            }
             acc[t] = o;
             l[t] = l[t] * sc + psum;
         }
@@ -561,8 +571,9 @@ long long att_ws_floats(long long B, long long Kq, long long N) {
     return (B > 0 ? B : 1) * nsplit * kHeads * Kq * 18;
 }
 
+template <typename... DROP>
 int launch_attention(const float *q, const float *k, const float *v, int B, int Kq, int N, float *ws, float *out, hipStream_t s,
-                     float *stats = nullptr) {
+                     float *stats, DROP... drop) {
     int sl, tl;
     att_geometry(N, &sl, &tl);
     // A workgroup takes 4 * QB blocks of 16 queries (wave w the blocks w, w + 4, ...).  Many keys: up to four blocks per wave, so
@@ -576,8 +587,8 @@ int launch_attention(const float *q, const float *k, const float *v, int B, int 
     float *pacc = ws, *pml = ws ? ws + (size_t)B * nsplit * kHeads * Kq * 16 : nullptr;
     const dim3 grid(nsplit, kHeads, B * nchunk);
 #define FNP_ATT(QB)                                                                                                              \
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(tf_attn_kernel<QB>), grid, dim3(kAttThreads), 0, s, q, k, v, Kq, N, sl, nsplit, nchunk, pacc, \
-                       pml, out, stats)
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(tf_attn_kernel<QB, DROP...>), grid, dim3(kAttThreads), 0, s, q, k, v, Kq, N, sl, nsplit, nchunk, \
+                       pacc, pml, out, stats, drop...)
     if (qb == 1) FNP_ATT(1);
     else if (qb == 2) FNP_ATT(2);
     else if (qb == 3) FNP_ATT(3);
@@ -591,6 +602,10 @@ int launch_attention(const float *q, const float *k, const float *v, int B, int 
         FNP_LAUNCH_CHECK();
     }
     return FNP_OK;
+}
+
+int launch_attention(const float *q, const float *k, const float *v, int B, int Kq, int N, float *ws, float *out, hipStream_t s) {
+    return launch_attention(q, k, v, B, Kq, N, ws, out, s, nullptr);
 }
 
 int launch_kv_proj(const float *x, const float *pe, int pe_batched, const float *wkv, const float *bkv, int B, int N, float *Ko, float *Vo,
@@ -637,6 +652,21 @@ extern "C" int fnp_tf_attention_stats(const float *q, const float *k, const floa
     const long long need = att_ws_floats(batch_size, num_queries, num_keys) * 4;
     if (need && (!workspace || workspace_bytes < need)) return FNP_ERR_WORKSPACE;
     return launch_attention(q, k, v, batch_size, num_queries, (int)num_keys, (float *)workspace, out, (hipStream_t)stream, stats);
+}
+
+// fnp_tf_attention_stats with the dropout instantiation of the attention kernel: out is the dropped output, stats are the plain ones
+extern "C" int fnp_tf_attention_dropout_stats(const float *q, const float *k, const float *v, int batch_size, int num_queries,
+                                              int64_t num_keys, void *workspace, int64_t workspace_bytes, float *out, float *stats,
+                                              float p, const uint64_t *seed, fnp_stream_t stream) {
+    if (!att_shape_ok(batch_size, num_queries, num_keys) || !(p >= 0.f && p < 1.f)) return FNP_ERR_ARG;
+    if (batch_size == 0) return FNP_OK;
+    if (!q || !k || !v || !out || !stats || !seed || ((uintptr_t)seed & 7)) return FNP_ERR_ARG;
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v | (uintptr_t)out | (uintptr_t)stats | (uintptr_t)workspace) & 15) return FNP_ERR_ARG;
+    const long long need = att_ws_floats(batch_size, num_queries, num_keys) * 4;
+    if (need && (!workspace || workspace_bytes < need)) return FNP_ERR_WORKSPACE;
+    const uint32_t threshold = fnp_dropout_threshold(p);
+    return launch_attention(q, k, v, batch_size, num_queries, (int)num_keys, (float *)workspace, out, (hipStream_t)stream, stats,
+                            fnp_dropout_args{(const unsigned long long *)seed, threshold, fnp_dropout_scale(threshold)});
 }
 
 extern "C" int64_t fnp_tf_decoder_workspace_bytes(int batch_size, int num_queries, int64_t num_keys, int ffn, int n_head_out) {

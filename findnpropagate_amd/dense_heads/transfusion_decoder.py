@@ -6,7 +6,9 @@ seven launches of csrc/tfdecoder.hip (eight with more than 256 queries) on one s
 
 SeparateHead_Transfusion keeps the reference's names and init.  attention(q, k, v) is the attention kernel alone;
 attention_autograd(q, k, v) is the same forward (bit for bit) with a backward on csrc/tfattn_grad.hip, which the decoder layer's
-opt-in fused_attention_grad route uses for its cross attention under autograd.
+opt-in fused_attention_grad route uses for its cross attention under autograd.  With dropout_p > 0 it applies dropout to the
+probabilities inside the kernels, by a counter-based mask of a device-side seed that the backward regenerates (include/fnp.h;
+the layer's fused_attention_dropout).
 DecoderHead(decoder, prediction_head)(query_feat, lidar_feat_flatten, query_pos, bev_pos) returns the reference's res_layer
 dict with `center` already offset.  Both DecoderHead and TransformerDecoderLayer.forward fall back to the modules called
 plainly whenever decoder_plain_reasons() / heads_plain_reasons() find something against the device path.
@@ -108,10 +110,40 @@ def _workspace(L, fn, B, Kq, N, dev):
     return (torch.empty(ws_bytes // 4, dtype=torch.float32, device=dev) if ws_bytes else None), ws_bytes
 
 
-def attention_stats(q, k, v, out=None, stats=None):
+def check_dropout(dropout_p, seed, device=None):
+    """host-side argument checks of the dropout arguments (no library needed, nothing read from the seed) -> p as a float"""
+    p = float(dropout_p)
+    assert 0.0 <= p < 1.0, f"0 <= dropout_p < 1, got {dropout_p}"
+    if p > 0.0:
+        assert isinstance(seed, torch.Tensor) and seed.dtype == torch.int64 and seed.numel() == 1, "seed: one int64 on the device"
+        assert seed.is_cuda and (device is None or seed.device == device), "seed: on the device of q, k and v"
+    return p
+
+
+def draw_dropout_seed(device):
+    """one int64 drawn on `device` from torch's generator for that device (torch.manual_seed reproduces it): the seed of one
+    attention dropout mask.  No host read."""
+    return torch.empty(1, dtype=torch.int64, device=device).random_()
+
+
+def attention_dropout_mask(seed, B, Kq, N, p):
+    """keep(seed, scene, head, query, key) of include/fnp.h as a bool tensor (B, 8, Kq, N), written by the device function the
+    kernels call.  For tests and tools: no training path calls it."""
+    assert 0 <= B and 1 <= Kq <= MAX_QUERIES and 1 <= N < 2 ** 31 // D_MODEL
+    assert isinstance(seed, torch.Tensor) and seed.dtype == torch.int64 and seed.numel() == 1 and seed.is_cuda, "seed: one int64 on the device"
+    assert 0.0 <= float(p) < 1.0, f"0 <= p < 1, got {p}"
+    L = lib.load()
+    keep = torch.empty((B, N_HEAD, Kq, N), dtype=torch.uint8, device=seed.device)
+    lib.check(L.fnp_tf_attention_dropout_mask(lib.ptr(seed), float(p), B, Kq, N, lib.ptr(keep), lib.stream()), "fnp_tf_attention_dropout_mask")
+    return keep.bool()
+
+
+def attention_stats(q, k, v, out=None, stats=None, dropout_p=0.0, seed=None):
     """attention() that also returns the softmax statistics: -> out (B, Kq, 128), stats (B, 8, Kq, 2) holding (M, L) per scene,
-    head and query (include/fnp.h).  out has attention()'s bits.  No gradient; attention_autograd is the differentiable form."""
+    head and query (include/fnp.h).  out has attention()'s bits.  No gradient; attention_autograd is the differentiable form.
+    With dropout_p > 0 and seed (one int64 on the device) out is the dropped output (P o Z) V; stats do not see the mask."""
     B, Kq, N = check_attention(q, k, v)
+    p = check_dropout(dropout_p, seed, q.device)
     L = lib.load()
     lib.require_device(q, k, v)
     q, k, v = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
@@ -123,15 +155,21 @@ def attention_stats(q, k, v, out=None, stats=None):
     assert stats.shape == (B, N_HEAD, Kq, 2) and stats.dtype == torch.float32 and stats.is_contiguous()
     if B:
         ws, ws_bytes = _workspace(L, "fnp_tf_attention_workspace_bytes", B, Kq, N, q.device)
-        lib.check(L.fnp_tf_attention_stats(lib.ptr(q), lib.ptr(k), lib.ptr(v), B, Kq, N, lib.ptr(ws), ws_bytes, lib.ptr(out),
-                                           lib.ptr(stats), lib.stream()), "fnp_tf_attention_stats")
+        if p == 0.0:
+            lib.check(L.fnp_tf_attention_stats(lib.ptr(q), lib.ptr(k), lib.ptr(v), B, Kq, N, lib.ptr(ws), ws_bytes, lib.ptr(out),
+                                               lib.ptr(stats), lib.stream()), "fnp_tf_attention_stats")
+        else:
+            lib.check(L.fnp_tf_attention_dropout_stats(lib.ptr(q), lib.ptr(k), lib.ptr(v), B, Kq, N, lib.ptr(ws), ws_bytes, lib.ptr(out),
+                                                       lib.ptr(stats), p, lib.ptr(seed), lib.stream()), "fnp_tf_attention_dropout_stats")
     return out, stats
 
 
-def attention_backward(q, k, v, out, stats, d_out, dq=None, dk=None, dv=None):
+def attention_backward(q, k, v, out, stats, d_out, dq=None, dk=None, dv=None, dropout_p=0.0, seed=None):
     """fnp_tf_attention_backward on contiguous f32 device tensors: writes the gradients into whichever of dq (B, Kq, 128), dk
-    and dv (B, N, 128) are given and skips the others; out and stats as attention_stats returned them"""
+    and dv (B, N, 128) are given and skips the others; out and stats as attention_stats returned them, with the same dropout_p
+    and seed (then fnp_tf_attention_dropout_backward regenerates the forward's mask)"""
     B, Kq, N = check_attention(q, k, v)
+    p = check_dropout(dropout_p, seed, q.device)
     L = lib.load()
     lib.require_device(q, k, v, out, stats, d_out, dq, dk, dv)
     assert out.shape == q.shape and d_out.shape == q.shape and stats.shape == (B, N_HEAD, Kq, 2)
@@ -140,37 +178,58 @@ def attention_backward(q, k, v, out, stats, d_out, dq=None, dk=None, dv=None):
     assert all(t.dtype == torch.float32 for t in (out, stats, d_out))
     if B and (dq is not None or dk is not None or dv is not None):
         ws, ws_bytes = _workspace(L, "fnp_tf_attention_backward_workspace_bytes", B, Kq, N, q.device)
-        lib.check(L.fnp_tf_attention_backward(lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(out), lib.ptr(stats), lib.ptr(d_out), B, Kq, N,
-                                              lib.ptr(ws), ws_bytes, lib.ptr(dq), lib.ptr(dk), lib.ptr(dv), lib.stream()),
-                  "fnp_tf_attention_backward")
+        if p == 0.0:
+            lib.check(L.fnp_tf_attention_backward(lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(out), lib.ptr(stats), lib.ptr(d_out), B, Kq, N,
+                                                  lib.ptr(ws), ws_bytes, lib.ptr(dq), lib.ptr(dk), lib.ptr(dv), lib.stream()),
+                      "fnp_tf_attention_backward")
+        else:
+            lib.check(L.fnp_tf_attention_dropout_backward(lib.ptr(q), lib.ptr(k), lib.ptr(v), lib.ptr(out), lib.ptr(stats), lib.ptr(d_out),
+                                                          B, Kq, N, lib.ptr(ws), ws_bytes, lib.ptr(dq), lib.ptr(dk), lib.ptr(dv), p,
+                                                          lib.ptr(seed), lib.stream()), "fnp_tf_attention_dropout_backward")
     return dq, dk, dv
 
 
 class _AttentionGrad(torch.autograd.Function):
     """attention_stats forward, attention_backward (csrc/tfattn_grad.hip) backward.  Saved for the backward: q, k, v, out and
-    the (M, L) statistics (B, 8, Kq, 2); nothing with Kq x N elements exists at any time."""
+    the (M, L) statistics (B, 8, Kq, 2); nothing with Kq x N elements exists at any time.  With dropout the seed is saved too
+    (a copy: the caller may overwrite its tensor), so the backward's mask is the forward's whatever the generator did since."""
 
     @staticmethod
-    def forward(ctx, q, k, v):
+    def forward(ctx, q, k, v, dropout_p, seed):
         q, k, v = q.detach().contiguous(), k.detach().contiguous(), v.detach().contiguous()
-        out, stats = attention_stats(q, k, v)
-        ctx.save_for_backward(q, k, v, out, stats)
+        ctx.dropout_p = dropout_p
+        if dropout_p > 0.0:
+            seed = seed.detach().clone()
+            out, stats = attention_stats(q, k, v, dropout_p=dropout_p, seed=seed)
+            ctx.save_for_backward(q, k, v, out, stats, seed)
+        else:
+            out, stats = attention_stats(q, k, v)
+            ctx.save_for_backward(q, k, v, out, stats)
         return out
 
     @staticmethod
     @torch.autograd.function.once_differentiable
     def backward(ctx, d_out):
-        q, k, v, out, stats = ctx.saved_tensors
+        q, k, v, out, stats, *seed = ctx.saved_tensors
         grads = [torch.empty_like(t) if need else None for t, need in zip((q, k, v), ctx.needs_input_grad)]
-        attention_backward(q, k, v, out, stats, d_out.contiguous(), *grads)
-        return tuple(grads)
+        if seed:
+            attention_backward(q, k, v, out, stats, d_out.contiguous(), *grads, dropout_p=ctx.dropout_p, seed=seed[0])
+        else:
+            attention_backward(q, k, v, out, stats, d_out.contiguous(), *grads)
+        return (*grads, None, None)
 
 
-def attention_autograd(q, k, v):
+def attention_autograd(q, k, v, dropout_p=0.0, seed=None):
     """attention(q, k, v) under autograd: the same values bit for bit, and gradients for whichever of q, k, v require them
-    (dq, dk, dv of softmax(0.25 q.k) v; the scores are recomputed tile by tile, never stored).  A second derivative raises."""
+    (dq, dk, dv of softmax(0.25 q.k) v; the scores are recomputed tile by tile, never stored).  A second derivative raises.
+    dropout_p > 0: dropout on the probabilities inside the kernels, the mask of include/fnp.h regenerated in the backward from
+    `seed` (one int64 on the device; None draws one with draw_dropout_seed)."""
     check_attention(q, k, v)
-    return _AttentionGrad.apply(q, k, v)
+    p = float(dropout_p)
+    if p > 0.0 and seed is None:
+        seed = draw_dropout_seed(q.device)
+    p = check_dropout(p, seed, q.device)
+    return _AttentionGrad.apply(q, k, v, p, seed if p > 0.0 else None)
 
 
 # ---- path selection ----------------------------------------------------------------------------------------------------------

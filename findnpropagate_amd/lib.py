@@ -215,6 +215,9 @@ SIGNATURES = {
     "fnp_tf_attention_backward_geometry": (c_int, [c_int64, POINTER(c_int), POINTER(c_int)]),
     "fnp_tf_attention_backward_workspace_bytes": (c_int64, [c_int, c_int, c_int64]),
     "fnp_tf_attention_backward": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int64, P, c_int64, P, P, P, P]),
+    "fnp_tf_attention_dropout_stats": (c_int, [P, P, P, c_int, c_int, c_int64, P, c_int64, P, P, c_float, P, P]),
+    "fnp_tf_attention_dropout_backward": (c_int, [P, P, P, P, P, P, c_int, c_int, c_int64, P, c_int64, P, P, P, c_float, P, P]),
+    "fnp_tf_attention_dropout_mask": (c_int, [P, c_float, c_int, c_int, c_int64, P, P]),
     "fnp_tf_decoder_workspace_bytes": (c_int64, [c_int, c_int, c_int64, c_int, c_int]),
     "fnp_tf_decoder": (c_int, [P, P, P, P, c_int, P, c_int64, c_int, c_int, c_int64, c_int, c_int, POINTER(c_int), c_int, P, c_int64,
                                P, P, P]),

@@ -89,10 +89,14 @@ class TransformerDecoderLayer(nn.Module):
     # softmax(0.25 q.k) v on the library's differentiable kernels (dense_heads.transfusion_decoder.attention_autograd) instead
     # of materialising the 8 x Pq x Pk scores.  A plain attribute: not a constructor argument, not in the state_dict.
     fused_attention_grad = False
+    # Opt-in on top of fused_attention_grad: in train() with multihead_attn.dropout > 0 the fused route applies that dropout
+    # inside the kernels (a counter-based mask from a freshly drawn seed, regenerated in the backward; include/fnp.h), where
+    # forward_plain draws torch's mask: the same distribution, other bits.  A plain attribute like the one above.
+    fused_attention_dropout = False
 
     def fused_grad_reasons(self, query, key, query_pos, key_pos, key_padding_mask=None, attn_mask=None):
-        """what stands against forward_fused_grad, as a list of short strings (empty: it can run).  Attention dropout is not in
-        the kernels: a layer in train() with multihead_attn.dropout > 0 keeps forward_plain."""
+        """what stands against forward_fused_grad, as a list of short strings (empty: it can run).  A layer in train() with
+        multihead_attn.dropout > 0 keeps forward_plain unless fused_attention_dropout is set."""
         from ..dense_heads.transfusion_decoder import D_MODEL, MAX_QUERIES, N_HEAD
 
         r = []
@@ -101,7 +105,7 @@ class TransformerDecoderLayer(nn.Module):
         mha = self.multihead_attn
         if mha.embed_dim != D_MODEL or mha.num_heads != N_HEAD or mha.in_proj_weight is None or mha.in_proj_bias is None:
             r.append("d_model / nhead")
-        if self.training and mha.dropout != 0:
+        if self.training and mha.dropout != 0 and not (self.fused_attention_dropout and 0 < mha.dropout < 1):
             r.append("attention dropout")
         tensors = [query, key, query_pos, key_pos] + list(self.parameters()) + [b for b in self.buffers() if b.is_floating_point()]
         if any(t.dtype != torch.float32 for t in tensors):
@@ -129,23 +133,27 @@ class TransformerDecoderLayer(nn.Module):
 
     def forward_fused_grad(self, query, key, query_pos, key_pos):
         """forward_plain with the cross attention's core on the differentiable kernels: the in- and out-projections stay
-        F.linear, everything else the same torch ops in the same order.  No masks, no attention dropout (fused_grad_reasons)."""
+        F.linear, everything else the same torch ops in the same order.  No masks; attention dropout in train() only with
+        fused_attention_dropout, inside the kernels (fused_grad_reasons)."""
         return self._forward_torch(query, key, query_pos, key_pos, None, None, self._cross_fused)
 
     def _cross_plain(self, q_in, m, key_padding_mask, attn_mask):
         return self.multihead_attn(query=q_in, key=m, value=m, key_padding_mask=key_padding_mask, attn_mask=attn_mask)[0]
 
     def _cross_fused(self, q_in, m, key_padding_mask, attn_mask):
-        """nn.MultiheadAttention(q_in (Pq, B, C), m, m)[0] without masks and dropout, on (B, L, 128) rows"""
-        from ..dense_heads.transfusion_decoder import attention_autograd
+        """nn.MultiheadAttention(q_in (Pq, B, C), m, m)[0] without masks, on (B, L, 128) rows; its dropout on the probabilities
+        (train() only) runs inside the kernels, on a seed drawn here"""
+        from ..dense_heads import transfusion_decoder as TD
 
         mha = self.multihead_attn
+        p = mha.dropout if self.training and self.fused_attention_dropout else 0.0
         w, b, d = mha.in_proj_weight, mha.in_proj_bias, mha.embed_dim
         rows_q, rows_m = q_in.transpose(0, 1), m.transpose(0, 1)
         q = F.linear(rows_q, w[:d], b[:d])
         k = F.linear(rows_m, w[d:2 * d], b[d:2 * d])
         v = F.linear(rows_m, w[2 * d:], b[2 * d:])
-        return F.linear(attention_autograd(q, k, v), mha.out_proj.weight, mha.out_proj.bias).transpose(0, 1)
+        core = TD.attention_autograd(q, k, v, p, TD.draw_dropout_seed(q.device)) if p > 0 else TD.attention_autograd(q, k, v)
+        return F.linear(core, mha.out_proj.weight, mha.out_proj.bias).transpose(0, 1)
 
     def _forward_torch(self, query, key, query_pos, key_pos, key_padding_mask, attn_mask, cross):
         q_pe = None if self.self_posembed is None else _rows(self.self_posembed(query_pos))

@@ -1004,6 +1004,51 @@ int fnp_tf_attention_backward(const float *q, const float *k, const float *v, co
                               const float *d_out, int batch_size, int num_queries, int64_t num_keys, void *workspace,
                               int64_t workspace_bytes, float *dq, float *dk, float *dv, fnp_stream_t stream);
 
+/* Attention dropout inside the differentiable attention core (additive, ABI 14; csrc/tfattn_dropout.h states the mask, the
+ * kernels are the dropout instantiations of the ones above).  Dropout sits after the softmax: O = (P o Z) V with
+ * Z_ij = keep_ij / (1 - p_eff).  The statistics (M, L) do not see the mask.  Backward: dV_j = sum_i P_ij Z_ij dO_i,
+ * dS_ij = P_ij (Z_ij dP_ij - D_i) with D_i = dO_i . O_i of the DROPPED output (sum_j P_ij Z_ij dP_ij = dO_i . O_i), dK and dQ
+ * from dS as above.  No mask is stored: every kernel regenerates its bits.
+ *
+ * The mask.  keep(seed, scene, head, query, key) is a pure function of those five integers; it depends on nothing of a launch
+ * (split length, query chunk, batch size, which kernel asks).  seed is a uint64, scene the index in the batch, head 0..7, query
+ * and key the row indices.
+ *   generator  Philox4x32-10 (Salmon et al. 2011): multipliers 0xD2511F53 (on word 0) and 0xCD9E8D57 (on word 2), the key words
+ *              advance by 0x9E3779B9 and 0xBB67AE85 after every round, ten rounds; a round maps (c0, c1, c2, c3) to
+ *              (hi(M1 c2) ^ c1 ^ k0, lo(M1 c2), hi(M0 c0) ^ c3 ^ k1, lo(M0 c0)).
+ *   key        (seed & 0xffffffff, seed >> 32)
+ *   counter    (key >> 2, query, scene * 8 + head, 0)
+ *   word       output word (key & 3) of that call belongs to `key`: one call serves an aligned group of four keys of a query
+ *   keep       iff word >= T, T = (uint32)((double)p * 2^32) with p the f32 argument; p_eff = T / 2^32 (|p_eff - p| < 2^-32;
+ *              p = 0.5 gives exactly 0.5), and the scale 1 / (1 - p_eff) is evaluated in double and rounded to f32 once (2 at
+ *              p = 0.5, 1 at p = 0).
+ * Because the scene index is part of the counter, a scene alone has the mask of scene 0: a batch and its FIRST scene alone agree
+ * bit for bit, other scenes get other masks (unlike the plain entry points, whose results do not depend on the position in a batch).
+ * Same seed, same bits, from run to run.
+ *
+ * seed is a DEVICE pointer to one uint64, 8-byte aligned; the kernels read it (no host read, and a captured graph does not
+ * freeze the mask: it replays with whatever the word holds then).  0 <= p < 1, anything else (NaN included) is FNP_ERR_ARG.
+ *
+ * fnp_tf_attention_dropout_stats: fnp_tf_attention_stats' arguments, workspace and launches; out is the dropped output, stats are
+ * bit for bit what fnp_tf_attention_stats writes.  fnp_tf_attention_dropout_backward: fnp_tf_attention_backward's arguments,
+ * workspace, launches and NULL-result rules; out is the dropped output and p, seed those of the forward.  With p = 0 (T = 0,
+ * every word kept, scale 1) both give the bits of the plain entry points.  In the key-stationary kernel a lane holds four queries
+ * against one key: lane i of a quad calls the generator for (query 4g + (i & 3), the quad's common key group) and the four lanes
+ * exchange their keep bits by quad permutes.  Rows past Kq and keys past N enter with P = 0; their mask bits are computed like any
+ * other and index nothing.
+ *
+ * fnp_tf_attention_dropout_mask: keep as one byte (0 or 1) per element of (B, 8, Kq, N), from the same device function the three
+ * kernels call; B * 8 <= 65535.  For tests and tools: nothing on a training path launches it. */
+int fnp_tf_attention_dropout_stats(const float *q, const float *k, const float *v, int batch_size, int num_queries, int64_t num_keys,
+                                   void *workspace, int64_t workspace_bytes, float *out, float *stats, float p, const uint64_t *seed,
+                                   fnp_stream_t stream);
+int fnp_tf_attention_dropout_backward(const float *q, const float *k, const float *v, const float *out, const float *stats,
+                                      const float *d_out, int batch_size, int num_queries, int64_t num_keys, void *workspace,
+                                      int64_t workspace_bytes, float *dq, float *dk, float *dv, float p, const uint64_t *seed,
+                                      fnp_stream_t stream);
+int fnp_tf_attention_dropout_mask(const uint64_t *seed, float p, int batch_size, int num_queries, int64_t num_keys, uint8_t *keep,
+                                  fnp_stream_t stream);
+
 /* Hungarian assignment and per-query targets of TransFusionHead (transfusion_head.py:352-444, hungarian_assigner.py:61-132;
  * additive, ABI 14; csrc/tfassign.hip).  The batch goes in four launches (valid rows, cost, match, targets); every device call
  * takes a stream, allocates nothing, calls no synchronising HIP function and uses no atomics: results are bit-identical from

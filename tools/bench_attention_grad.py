@@ -14,8 +14,13 @@ kernels   the library's calls on their own, same events, raw ctypes calls on pre
           head and product: 2 products forward, 3 for dq, 4 for dk and dv) and its share of 157.3 TFLOP/s.
 memory    torch.cuda.max_memory_allocated over one forward + backward of either path, above what was allocated before it
           (inputs, d_out); one score tensor is 8 x K x N x 4 bytes per scene.
+dropout   --dropout P (0 < P < 1): the fused span is attention_autograd(q, k, v, P, seed) (the dropout instantiations of the three
+          kernels, the mask regenerated from one seed on the device), the torch span the same expression with F.dropout(P) on the
+          probabilities, and the kernels on their own are the fnp_tf_attention_dropout_* calls.  The two spans draw different
+          masks, so no difference of gradients is reported (tests/test_gpu_attention_dropout.py holds the values).  Without
+          --dropout every call is the plain one: run both in one session to see what the mask costs per kernel.
 
-    python tools/bench_attention_grad.py [--reps 20] [--inner 5] [--batches 1 4]
+    python tools/bench_attention_grad.py [--reps 20] [--inner 5] [--batches 1 4] [--dropout 0.1]
 """
 import argparse
 import json
@@ -73,12 +78,23 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--inner", type=int, default=5)
     ap.add_argument("--batches", type=int, nargs="*", default=[1, 4])
+    ap.add_argument("--dropout", type=float, default=0.0)
     a = ap.parse_args()
+    P = a.dropout
+    assert 0.0 <= P < 1.0
     dev = torch.device("cuda", 0)
     L = lib.load()
     rng = np.random.default_rng(0)
     out = {"metric": "attention_core_forward_backward", "queries": K, "keys": N, "split_len": TD.attention_geometry(N)[0],
-           "backward_key_block": TD.attention_backward_geometry(N)[0]}
+           "backward_key_block": TD.attention_backward_geometry(N)[0], "dropout_p": P}
+    seed = torch.tensor([0x0123456789ABCDEF], dtype=torch.int64, device=dev)
+
+    def torch_dropout(q, k, v):
+        B = q.shape[0]
+        heads = lambda t, rows: t.reshape(B, rows, HEADS, 16).transpose(1, 2)
+        p = torch.softmax(0.25 * (heads(q, K) @ heads(k, N).transpose(2, 3)), dim=-1)
+        return (torch.nn.functional.dropout(p, P) @ heads(v, N)).transpose(1, 2).reshape(B, K, D)
+
     t = lambda *shape: torch.from_numpy(rng.normal(0, 1, shape).astype(np.float32)).to(dev)
     for B in a.batches:
         q, k, v, d_out = t(B, K, D), t(B, N, D), t(B, N, D), t(B, K, D)
@@ -88,13 +104,17 @@ def main():
             q.grad = k.grad = v.grad = None
             fn(q, k, v).backward(d_out)
 
-        fused, plain = (lambda: span(TD.attention_autograd)), (lambda: span(RG.attention_torch))
-        fused()
-        got = [x.grad.clone() for x in (q, k, v)]
-        plain()
-        res = {"max_abs_difference": {n: float((g - x.grad).abs().max()) for n, g, x in zip(("dq", "dk", "dv"), got, (q, k, v))}}
-        q.grad = k.grad = v.grad = None
-        del got
+        if P > 0:
+            fused, plain = (lambda: span(lambda *x: TD.attention_autograd(*x, P, seed))), (lambda: span(torch_dropout))
+            res = {}
+        else:
+            fused, plain = (lambda: span(TD.attention_autograd)), (lambda: span(RG.attention_torch))
+            fused()
+            got = [x.grad.clone() for x in (q, k, v)]
+            plain()
+            res = {"max_abs_difference": {n: float((g - x.grad).abs().max()) for n, g, x in zip(("dq", "dk", "dv"), got, (q, k, v))}}
+            q.grad = k.grad = v.grad = None
+            del got
         res["score_tensor_bytes"] = HEADS * K * N * 4 * B
         res["fused_peak_bytes"], res["torch_peak_bytes"] = peak(fused), peak(plain)
         for _ in range(3):
@@ -109,7 +129,7 @@ def main():
         # the library's calls on their own: preallocated buffers, no wrapper, no allocation between the events
         with torch.no_grad():
             qd, kd, vd = q.detach(), k.detach(), v.detach()
-            o, st = TD.attention_stats(qd, kd, vd)
+            o, st = TD.attention_stats(qd, kd, vd, dropout_p=P, seed=seed)
             dq, dk, dv = torch.empty_like(qd), torch.empty_like(kd), torch.empty_like(vd)
             fw_bytes, bw_bytes = L.fnp_tf_attention_workspace_bytes(B, K, N), L.fnp_tf_attention_backward_workspace_bytes(B, K, N)
             fw, bw = torch.empty(fw_bytes // 4, device=dev), torch.empty(bw_bytes // 4, device=dev)
@@ -119,6 +139,13 @@ def main():
             backward = lambda a_, b_, c_: lib.check(L.fnp_tf_attention_backward(
                 lib.ptr(qd), lib.ptr(kd), lib.ptr(vd), lib.ptr(o), lib.ptr(st), lib.ptr(d_out), B, K, N, lib.ptr(bw), bw_bytes,
                 lib.ptr(a_), lib.ptr(b_), lib.ptr(c_), stream), "fnp_tf_attention_backward")
+            if P > 0:
+                forward = lambda: lib.check(L.fnp_tf_attention_dropout_stats(
+                    lib.ptr(qd), lib.ptr(kd), lib.ptr(vd), B, K, N, lib.ptr(fw), fw_bytes, lib.ptr(o), lib.ptr(st), P, lib.ptr(seed),
+                    stream), "fnp_tf_attention_dropout_stats")
+                backward = lambda a_, b_, c_: lib.check(L.fnp_tf_attention_dropout_backward(
+                    lib.ptr(qd), lib.ptr(kd), lib.ptr(vd), lib.ptr(o), lib.ptr(st), lib.ptr(d_out), B, K, N, lib.ptr(bw), bw_bytes,
+                    lib.ptr(a_), lib.ptr(b_), lib.ptr(c_), P, lib.ptr(seed), stream), "fnp_tf_attention_dropout_backward")
             product = 2 * B * K * N * D
             calls = {"forward_with_stats": (forward, 2), "backward_dq": (lambda: backward(dq, None, None), 3),
                      "backward_dk_dv": (lambda: backward(None, dk, dv), 4), "backward_all": (lambda: backward(dq, dk, dv), 7)}
