@@ -235,6 +235,9 @@ SIGNATURES = {
                                            c_double, c_double, POINTER(c_float), POINTER(c_float), c_double, P, P, POINTER(c_void_p), P]),
     "fnp_tf_assign_targets": (c_int, [P, P, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_double, c_float, c_float, c_uint64,
                                       P, P, P, P, P, P, P]),
+    "fnp_adam_onecycle_workspace_bytes": (c_int64, [c_int64]),
+    "fnp_adam_onecycle_step": (c_int, [c_int, c_int64, P, P, P, P, P, P, P, P, c_double, c_double, c_double, c_double, c_double,
+                                       c_double, c_double, c_double, c_int, P, c_int64, P, P, P]),
 }
 
 

@@ -1140,6 +1140,52 @@ int fnp_tf_query_loss_backward(const void *heatmap, const void *const *heads, co
                                const float *code_weights, const float *unknown_code_weights, double unknown_cls_weight,
                                const float *grad_out, void *grad_heatmap, void *const *grad_heads, fnp_stream_t stream);
 
+/* The optimizer step of the reference's adam_onecycle recipe (tools/train_utils/train_utils.py:173-176 around
+ * optimization/fastai_optim.py OptimWrapper.step with true_wd and torch's Adam; additive, ABI 14; csrc/optim.hip): unscale,
+ * non-finite check, gradient norm, clip, decoupled weight decay, Adam and the loss-scale update in THREE launches whatever the
+ * number of tensors, with no host read, no allocation and no atomics: results are bit-identical from run to run.
+ *
+ * Host inputs, by value: lr, beta1, beta2, eps, wd, max_norm (doubles; lr and beta1 move every step with the OneCycle schedule;
+ * max_norm = +infinity: no clipping), growth_factor, backoff_factor, growth_interval (the loss scaler's; ignored when scale is NULL).
+ * Device state: per tensor i of num_tensors: params[i], exp_avg[i], exp_avg_sq[i] (f32, contiguous, 4-byte aligned, the
+ * tensor's length each) and steps[i] (int32); the scaler's scale (1 f32) and growth_tracker (1 int32), both NULL without a
+ * scaler (the scale is then 1); outputs grad_norm (1 f32) and found_inf (1 int32).  params, grads, exp_avg and exp_avg_sq are
+ * DEVICE tables of num_tensors pointers each; grads[i] == NULL: tensor i has no gradient this step.  Gradients are f32 and are
+ * left as they came (scaled, unclipped).
+ * chunks: a DEVICE table of num_chunks struct fnp_optim_chunk, made once per parameter list: workgroup c works on elements
+ * [offset, offset + length) of tensor `tensor`; 0 < length, offset a multiple of 4, every element of every tensor in exactly
+ * one chunk (an empty tensor has none), chunks of a tensor in ascending order.  The chunk length is the caller's choice.
+ *
+ * The step (m = exp_avg, v = exp_avg_sq, t = steps):
+ *   1. inv = (float)(1.0 / (double)scale);  g^ = g * inv (f32);  found_inf = any g^ of any present gradient is not finite.
+ *   2. N = sqrt(sum g^ * g^) over all present gradients, the squares formed and summed in f64: per chunk by a fixed tree, the
+ *      chunks' partial sums in a fixed order;  c = (float)min(1, max_norm / (N + 1e-6)).
+ *   3. found_inf: no byte of any p, m, v, t is written;  scale <- scale * backoff_factor;  growth_tracker <- 0.
+ *   4. otherwise every tensor, with a gradient or not: p <- p * (float)(1 - wd * lr).
+ *   5. then every tensor with a gradient: t <- t + 1;  g' = g^ * c;  m <- m + (g' - m) * (float)(1 - beta1);
+ *      v <- (float)beta2 * v + (float)(1 - beta2) * g' * g';
+ *      p <- p - (float)(lr / (1 - beta1^t)) * (m / (sqrt(v) / (float)sqrt(1 - beta2^t) + (float)eps)),
+ *      the bias corrections in f64 from the tensor's own t and this step's beta1; f32 IEEE multiply, add, divide and square
+ *      root, no fused multiply-add.
+ *   6. then growth_tracker <- growth_tracker + 1, and when that equals growth_interval: scale <- scale * growth_factor if that
+ *      is finite, growth_tracker <- 0.
+ * grad_norm <- (float)N and found_inf are written by every step.  A non-finite gradient skips the step also without a scaler.
+ * workspace: fnp_adam_onecycle_workspace_bytes(num_chunks) bytes, 8-byte aligned; its contents mean nothing between steps.
+ * Every host-visible argument is checked before the first launch (lr, eps >= 0 and wd finite, the betas in [0, 1), max_norm >= 0
+ * or +infinity, the scaler's factors positive and finite, growth_interval >= 1; FNP_ERR_ARG otherwise): a call that returns an
+ * error has written nothing.  What the device tables hold is the caller's to get right. */
+struct fnp_optim_chunk {
+    int32_t tensor;
+    int32_t length;
+    int64_t offset;
+};
+int64_t fnp_adam_onecycle_workspace_bytes(int64_t num_chunks);
+int fnp_adam_onecycle_step(int num_tensors, int64_t num_chunks, const struct fnp_optim_chunk *chunks, float *const *params,
+                           const float *const *grads, float *const *exp_avg, float *const *exp_avg_sq, int32_t *steps,
+                           float *scale, int32_t *growth_tracker, double lr, double beta1, double beta2, double eps, double wd,
+                           double max_norm, double growth_factor, double backoff_factor, int growth_interval, void *workspace,
+                           int64_t workspace_bytes, float *grad_norm, int32_t *found_inf, fnp_stream_t stream);
+
 /* Capacity overflow: data-dependent counts (n_voxels, n_out) always hold the TRUE count; every
  * kernel clamps to the capacity it was given, so a count larger than its capacity means rows
  * were dropped and the caller must re-run with larger buffers. */

@@ -15,7 +15,11 @@ ap.add_argument("--amp", action="store_true", help="the reference's AMP recipe (
                 "GradScaler, unscale_, clip_grad_norm_(10), scaler.step / update")
 ap.add_argument("--through-bev", action="store_true", help="also time the step with the loss (mean of squares) on spatial_features_2d: HeightCompression "
                 "(differentiable densify) + BaseBEVBackbone in train mode (the reference's torch modules, transfusion_lidar.yaml's BEV config)")
+ap.add_argument("--optimizer", default="sgd", choices=["sgd", "adam_onecycle", "adam_onecycle_fused"], help="sgd: torch.optim.SGD, every round's definition of "
+                "`train_step_ms`; adam_onecycle: the reference's own recipe (transfusion_lidar.yaml) on the mirrored OptimWrapper and OneCycle; "
+                "adam_onecycle_fused: the same on FusedAdamOneCycle.step_scaled (one device-resident step, in-place zero_grad)")
 args = ap.parse_args()
+assert args.optimizer == "sgd" or not args.through_bev, "--through-bev steps with SGD only"
 dev = torch.device("cuda", 0); B = args.batch
 grid = np.round((np.array(syn.POINT_CLOUD_RANGE[3:]) - np.array(syn.POINT_CLOUD_RANGE[:3])) / np.array(syn.VOXEL_SIZE)).astype(int)
 net = syn.init_backbone_weights(VoxelResBackBone8x({"USE_BIAS": False, "FNP_DTYPE": args.dtype}, 5, grid), 0).to(dev)
@@ -25,7 +29,16 @@ cfg = S.make_voxel_cfg(syn.VOXEL_SIZE, syn.POINT_CLOUD_RANGE, 5, 10, 120000 if a
 vox = S.voxelize(torch.from_numpy(pts).to(dev), torch.from_numpy(off).to(dev), B, cfg)
 n = int(vox["n"].item())
 bd = lambda: {"voxel_features": vox["mean"][:n], "voxel_coords": vox["coords"][:n].float(), "batch_size": B}
-opt = torch.optim.SGD(net.parameters(), lr=1e-4)
+sched, iters = None, [0]
+if args.optimizer == "sgd":
+    opt = torch.optim.SGD(net.parameters(), lr=1e-4)
+else:
+    from findnpropagate_amd.train_utils.optimization import LossScaler, build_optimizer, build_scheduler
+    ocfg = {"OPTIMIZER": "adam_onecycle", "LR": 1e-3, "WEIGHT_DECAY": 0.01, "MOMS": [0.95, 0.85], "PCT_START": 0.4, "DIV_FACTOR": 10,
+            "FNP_FUSED_STEP": args.optimizer == "adam_onecycle_fused"}      # transfusion_lidar.yaml's OPTIMIZATION
+    opt = build_optimizer(net, ocfg)
+    sched = build_scheduler(opt, 10 ** 6, 1, -1, ocfg)[0]
+FUSED = args.optimizer == "adam_onecycle_fused"
 
 def fwd(all_outputs=True):
     # the stand-in loss: mean of squares.  all_outputs: over the four multi-scale tensors and the encoded tensor (`train_step_ms`, every
@@ -46,16 +59,22 @@ def timed(fn, reps):
     torch.cuda.synchronize()
     return float(np.median([evs[i].elapsed_time(evs[i + 1]) for i in range(reps)]))
 
-scaler = torch.amp.GradScaler("cuda", init_scale=2.0 ** 12) if args.amp else None
+scaler = (LossScaler(True, init_scale=2.0 ** 12) if FUSED else torch.amp.GradScaler("cuda", init_scale=2.0 ** 12)) if args.amp else None
 
 def step(all_outputs=True):
-    opt.zero_grad(set_to_none=True)
+    if sched is not None:
+        sched.step(iters[0], 0); iters[0] += 1
+    if args.optimizer == "sgd": opt.zero_grad(set_to_none=True)
+    else: opt.zero_grad()               # train_utils.py:167 (the fused class zeroes in place: its gradient addresses stay)
     if scaler is None:
         loss = fwd(all_outputs); loss.backward(); opt.step()
         return
     with torch.autocast("cuda", dtype=torch.float16):
         loss = fwd(all_outputs)
     scaler.scale(loss).backward()
+    if FUSED:
+        opt.step_scaled(scaler, 10.0)
+        return
     scaler.unscale_(opt)
     torch.nn.utils.clip_grad_norm_(net.parameters(), 10.0)      # optim_cfg.GRAD_NORM_CLIP of the nuScenes configs
     scaler.step(opt)
@@ -116,7 +135,7 @@ with torch.no_grad():
 net.eval()
 with torch.no_grad():
     ms_fwd_eval = timed(lambda: net(bd()), args.reps)   # fused inference path
-print(json.dumps({"batch": B, "sweeps": args.sweeps, "amp": bool(args.amp), "points": int(pts.shape[0]), "voxels": n, "dtype": "fp16 autocast" if args.amp else args.dtype,
+print(json.dumps({"optimizer": args.optimizer, "batch": B, "sweeps": args.sweeps, "amp": bool(args.amp), "points": int(pts.shape[0]), "voxels": n, "dtype": "fp16 autocast" if args.amp else args.dtype,
                   "train_step_ms": round(ms_step, 2),
                   "train_step_ms_loss_on_encoded_tensor_only": round(ms_step_enc, 2), "stand_in_loss_alone_ms": round(ms_loss, 2),
                   "module_forward_ms": round(ms_fwd_train, 2),
