@@ -11,7 +11,11 @@ module's cfg ('fp32' | 'bf16' | 'fp16') overrides it (the features are cast befo
 Training: when the encoded features require grad (and grad mode is on) the densification is differentiable
 (sparse.DenseFunction, backward fnp_sparse_to_dense_backward), as the reference's torch index assignment is, so the
 detector's loss reaches the 3D backbone; the OUT_DTYPE cast is a torch op on the graph.  Such an output is never the
-reused buffer."""
+reused buffer.
+
+FNP_DEFER_DENSE (model cfg, our addition, default off): write `spatial_features_stride` and NO `spatial_features` — for a
+BaseBEVBackbone that takes its first block from the sparse rows (FNP_SPARSE_FIRST / FNP_SPARSE_FIRST_TRAIN) and densifies by
+itself when it has to take the dense path: the 33 MB-per-scene map is then neither written nor back-propagated."""
 import torch
 import torch.nn as nn
 
@@ -26,10 +30,14 @@ class HeightCompression(nn.Module):
         self.reuse_output = bool(_get(model_cfg, "REUSE_OUTPUT", False))
         od = _get(model_cfg, "OUT_DTYPE", "keep")
         self.out_dtype = {"keep": None, "fp32": torch.float32, "bf16": torch.bfloat16, "fp16": torch.float16}[str(od).lower()]
+        self.defer_dense = bool(_get(model_cfg, "FNP_DEFER_DENSE", False))
         self._ws = None
         self._out = None
 
     def forward(self, batch_dict):
+        if self.defer_dense:
+            batch_dict["spatial_features_stride"] = batch_dict["encoded_spconv_tensor_stride"]
+            return batch_dict
         t = batch_dict["encoded_spconv_tensor"]
         feats = t.features.contiguous()
         if self.out_dtype is not None and feats.dtype != self.out_dtype:

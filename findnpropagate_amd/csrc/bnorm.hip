@@ -13,6 +13,7 @@
 // that adds the partials in workgroup order) and an elementwise pass.  No atomics: results are bit-reproducible.
 // Row count lives in device memory (`n_rows`), so nothing synchronises with the host.
 #include "common.h"
+#include "rowvec.h"   // ldf / stf, load8 / store8, shfl_xor_f64 (shared with bev_bn.hip)
 
 namespace {
 
@@ -21,38 +22,6 @@ constexpr int kMaxParts = 256;   // statistics workgroups (one per CU; 1024 meas
                                  // 2.4x slower — 7.2 -> 17.5 us for 42 of them per step)
 constexpr int kUnroll = 4;       // rows a statistics thread requests per trip
 constexpr int kFinC = 16;        // channels per finishing workgroup
-
-__device__ __forceinline__ float ldf(const float *p, size_t i) { return p[i]; }
-__device__ __forceinline__ float ldf(const __bf16 *p, size_t i) { return (float)p[i]; }
-__device__ __forceinline__ float ldf(const _Float16 *p, size_t i) { return (float)p[i]; }
-__device__ __forceinline__ void stf(float *p, size_t i, float v) { p[i] = v; }
-__device__ __forceinline__ void stf(__bf16 *p, size_t i, float v) { p[i] = (__bf16)v; }
-__device__ __forceinline__ void stf(_Float16 *p, size_t i, float v) { p[i] = (_Float16)v; }
-
-// 8 consecutive channels of one row as floats
-template <typename T> __device__ __forceinline__ void load8(const T *p, float (&v)[8]) {
-    if constexpr (sizeof(T) == 2) {
-        const uint4 raw = *reinterpret_cast<const uint4 *>(p);
-        const T *e = reinterpret_cast<const T *>(&raw);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)e[j];
-    } else {
-        const float4 a = reinterpret_cast<const float4 *>(p)[0], b = reinterpret_cast<const float4 *>(p)[1];
-        v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
-    }
-}
-template <typename T> __device__ __forceinline__ void store8(T *p, const float (&v)[8]) {
-    if constexpr (sizeof(T) == 2) {
-        uint4 raw;
-        T *e = reinterpret_cast<T *>(&raw);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) e[j] = (T)v[j];
-        *reinterpret_cast<uint4 *>(p) = raw;
-    } else {
-        reinterpret_cast<float4 *>(p)[0] = make_float4(v[0], v[1], v[2], v[3]);
-        reinterpret_cast<float4 *>(p)[1] = make_float4(v[4], v[5], v[6], v[7]);
-    }
-}
 
 // Statistics pass.  MODE 0 (forward): a = x, b = x * x.  MODE 1 (backward): a = g, b = g * xhat.
 // part[(wg * C + c) * 2 + {0, 1}] = the workgroup's sums for channel c (f64).
@@ -67,12 +36,6 @@ constexpr int kStatThreads = 512;
 // whole waves; 32 lanes per row at most (C <= 256) must fit a wave-aligned workgroup; red[NW][32][16] f64 is 4 KB per wave of
 // static LDS: 1,024 threads sit exactly on the 64 KB limit
 static_assert(kStatThreads % 64 == 0 && kStatThreads >= 64 && kStatThreads <= 1024, "kStatThreads: a multiple of 64 in [64, 1024]");
-__device__ __forceinline__ double shfl_xor_f64(double v, int m) {
-    int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __shfl_xor(lo, m);
-    hi = __shfl_xor(hi, m);
-    return __hiloint2double(hi, lo);
-}
 template <typename T, int MODE>
 __global__ __launch_bounds__(kStatThreads) void bn_stats_kernel(const T *__restrict__ x, const T *__restrict__ dy,
                                                                 const T *__restrict__ y, const int *__restrict__ n_rows, int cap,

@@ -12,6 +12,7 @@
 //      a tile without sites only writes zeros.
 // Without a workspace the scatter path is used and `out` must be zero on entry.
 #include "common.h"
+#include "dense_tile.h"   // the cell -> row map, the tile geometry and the LDS stagings (shared with bev_bn.hip)
 #include <cstdint>
 
 namespace {
@@ -33,23 +34,13 @@ __global__ __launch_bounds__(kThreads) void dense_scatter_kernel(const T *__rest
     }
 }
 
-__global__ __launch_bounds__(kThreads) void dense_index_kernel(const int *__restrict__ coords, const int *__restrict__ n_rows,
-                                                               int cap, int B, int D, int H, int W, int *__restrict__ index) {
-    const int n = min(*n_rows, cap);
-    for (int r = blockIdx.x * kThreads + threadIdx.x; r < n; r += gridDim.x * kThreads) {
-        const int4 c = reinterpret_cast<const int4 *>(coords)[r];
-        if (c.x < 0 || c.x >= B || c.y < 0 || c.y >= D || c.z < 0 || c.z >= H || c.w < 0 || c.w >= W) continue;
-        index[(((long long)c.x * D + c.y) * H + c.z) * W + c.w] = r;
-    }
-}
-
 // T: element type (2 or 4 bytes); row bytes must be a multiple of 4.  One tile = 64*VEC consecutive cells
 // of a (b,z) plane; lane l owns cells VEC*l .. VEC*l+VEC-1 and stores them with one VEC*sizeof(T)-byte
 // store per channel plane (a wave store covers 64*VEC*sizeof(T) contiguous bytes).
 // LDS: kSlots rows of C*sizeof(T) + 4 bytes (the + 4 spreads the rows over the banks): the occupied
 // cells of a tile (~10 %) get consecutive slots; a tile with more than kSlots of them is written in VEC
 // passes of one cell per lane (element stores) — rare, and still each element exactly once.
-constexpr int kSlots = 64;
+constexpr int kSlots = kDenseSlots;
 
 template <typename T, int VEC>
 __global__ __launch_bounds__(kThreads) void dense_write_kernel(const T *__restrict__ feats, const int *__restrict__ index, int C,
@@ -58,7 +49,6 @@ __global__ __launch_bounds__(kThreads) void dense_write_kernel(const T *__restri
     // fill (optional, per channel): the value of a cell without a row instead of 0 — the BEV map behind a convolution whose
     // epilogue (BatchNorm shift, ReLU) gives cells with no input in reach a constant per channel
     extern __shared__ __attribute__((aligned(16))) unsigned char fnp_dense_smem[];
-    typedef int IVec __attribute__((ext_vector_type(VEC)));
     typedef T TVec __attribute__((ext_vector_type(VEC)));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long tile = blockIdx.x;
@@ -67,18 +57,7 @@ __global__ __launch_bounds__(kThreads) void dense_write_kernel(const T *__restri
     const int b = (int)(bz / D), z = (int)(bz % D);
     const bool in = l0 + (long long)VEC * lane < plane;          // (plane % VEC == 0: all of the lane's cells or none)
     int r[VEC];
-    if (in) {
-        if constexpr (VEC == 1) {
-            r[0] = index[bz * plane + l0 + lane];
-        } else {
-            const IVec v = *reinterpret_cast<const IVec *>(index + bz * plane + l0 + (long long)VEC * lane);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) r[j] = v[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) r[j] = -1;
-    }
+    fnp_dense_tile_rows<VEC>(index, bz * plane + l0 + (long long)VEC * lane, in, r);
     unsigned long long occ[VEC];                                  // same in all four waves
     int total = 0;
 #pragma unroll
@@ -91,20 +70,8 @@ __global__ __launch_bounds__(kThreads) void dense_write_kernel(const T *__restri
     const long long cstep = (long long)D * plane;
     const unsigned long long below = (1ull << lane) - 1ull;
 
-    // rows of the cells in mask m (taken from r[j]) -> slots first, first + 1, ...; wave w copies every 4th
     auto stage = [&](unsigned long long m, const int rj, int first) {
-        int k = first;
-        while (m) {
-            const int x = __ffsll((long long)m) - 1;
-            m &= m - 1;
-            const int rr = __shfl(rj, x);
-            const int slot = k++;
-            if ((slot & 3) != wave) continue;
-            const unsigned *src = reinterpret_cast<const unsigned *>(reinterpret_cast<const unsigned char *>(feats) + (size_t)rr * row_bytes);
-            unsigned *dst = reinterpret_cast<unsigned *>(fnp_dense_smem + slot * stride);
-            for (int q = lane; q * 4 < row_bytes; q += 64) dst[q] = src[q];
-        }
-        return k;
+        return fnp_dense_stage_rows(fnp_dense_smem, feats, row_bytes, stride, m, rj, first, lane, wave);
     };
 
     if (total == 0) {
@@ -148,11 +115,7 @@ __global__ __launch_bounds__(kThreads) void dense_write_kernel(const T *__restri
     }
 }
 
-// Cells per lane.  Measured on MI355X (16 scenes, 265 MB bf16): 2 -> 101 us (2.6 TB/s), 4 -> 120 us,
-// 8 -> 296 us (tiles of 256+ cells overflow the 64 LDS slots near the ego vehicle and take the element-
-// store path), 1 -> 134 us; memset + row scatter 264 us.
-constexpr int kDenseVec = 2;
-
+// (cells per lane: kDenseVec, dense_tile.h)
 template <typename T, int VEC>
 int launch_dense_write(const void *feats, const int *index, int C, int B, int D, long long plane, void *out, const float *fill, hipStream_t s) {
     const int row_bytes = C * (int)sizeof(T);
@@ -194,7 +157,7 @@ int run_dense(const void *feats, const int *coords, const int *n_rows, int cap, 
         const int frc = fnp_fill_words(index, cells, 0xffffffffu, s);
         if (frc) return frc;
     }
-    hipLaunchKernelGGL(dense_index_kernel, dim3(fnp_grid_for(cap, kThreads)), dim3(kThreads), 0, s, coords, n_rows, cap, B, D, H,
+    hipLaunchKernelGGL(fnp_dense_index_kernel, dim3(fnp_grid_for(cap, kThreads)), dim3(kThreads), 0, s, coords, n_rows, cap, B, D, H,
                        W, index);
     FNP_LAUNCH_CHECK();
     // widest store (<= 16 bytes per lane) that the plane size and the buffer alignment allow
@@ -246,8 +209,6 @@ __global__ __launch_bounds__(kThreads) void dense_grad_kernel(const T *__restric
                                                               int D, long long plane, int tiles_per_plane, int quad,
                                                               T *__restrict__ grad_feats) {
     extern __shared__ __attribute__((aligned(16))) unsigned char fnp_dense_smem[];
-    typedef int IVec __attribute__((ext_vector_type(VEC)));
-    typedef T TVec __attribute__((ext_vector_type(VEC)));
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
     const long long tile = blockIdx.x;
     const long long bz = tile / tiles_per_plane;
@@ -255,18 +216,7 @@ __global__ __launch_bounds__(kThreads) void dense_grad_kernel(const T *__restric
     const int b = (int)(bz / D), z = (int)(bz % D);
     const bool in = l0 + (long long)VEC * lane < plane;
     int r[VEC];
-    if (in) {
-        if constexpr (VEC == 1) {
-            r[0] = index[bz * plane + l0 + lane];
-        } else {
-            const IVec v = *reinterpret_cast<const IVec *>(index + bz * plane + l0 + (long long)VEC * lane);
-#pragma unroll
-            for (int j = 0; j < VEC; ++j) r[j] = v[j];
-        }
-    } else {
-#pragma unroll
-        for (int j = 0; j < VEC; ++j) r[j] = -1;
-    }
+    fnp_dense_tile_rows<VEC>(index, bz * plane + l0 + (long long)VEC * lane, in, r);
     const unsigned long long below = (1ull << lane) - 1ull;
     int total = 0, slot[VEC];                                    // slot of cell j (when occupied): rank among the tile's rows
 #pragma unroll
@@ -281,7 +231,6 @@ __global__ __launch_bounds__(kThreads) void dense_grad_kernel(const T *__restric
     int *slot_row = reinterpret_cast<int *>(fnp_dense_smem + kSlots * stride);
     const T *g = grad_out + ((long long)b * C * D + z) * plane + l0 + (long long)VEC * lane;   // channel c adds c * D * plane
     const long long cstep = (long long)D * plane;
-    constexpr int U = 8;                                         // channel planes in flight per wave
     for (int p0 = 0; p0 < total; p0 += kSlots) {                 // one pass unless the tile holds more than kSlots rows
         bool mine[VEC], any = false;
 #pragma unroll
@@ -291,22 +240,7 @@ __global__ __launch_bounds__(kThreads) void dense_grad_kernel(const T *__restric
             if (mine[j] && wave == 0) slot_row[slot[j] - p0] = r[j];
         }
         if (any) {
-            for (int c0 = wave; c0 < C; c0 += 4 * U) {
-                TVec v[U];
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (c0 + 4 * u < C) {
-                        if constexpr (VEC == 1) v[u][0] = g[(c0 + 4 * u) * cstep];
-                        else v[u] = *reinterpret_cast<const TVec *>(g + (c0 + 4 * u) * cstep);
-                    }
-#pragma unroll
-                for (int u = 0; u < U; ++u)
-                    if (c0 + 4 * u < C) {
-#pragma unroll
-                        for (int j = 0; j < VEC; ++j)
-                            if (mine[j]) reinterpret_cast<T *>(fnp_dense_smem + (slot[j] - p0) * stride)[c0 + 4 * u] = v[u][j];
-                    }
-            }
+            fnp_dense_gather_tile<T, VEC>(fnp_dense_smem, g, cstep, C, stride, wave, mine, slot, p0);
         }
         __syncthreads();
         const int cnt = min(total - p0, kSlots);

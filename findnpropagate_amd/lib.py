@@ -190,7 +190,11 @@ SIGNATURES = {
     "fnp_bn_workspace_bytes": (c_int64, [c_int]),
     "fnp_bn_train_forward": (c_int, [P, c_int, P, c_int, c_int, P, P, P, P, c_float, c_float, P, c_int, P, P, P, P, P, c_int64, P]),
     "fnp_bn_train_backward": (c_int, [P, P, P, c_int, P, c_int, c_int, P, P, P, c_int, P, P, P, P, P, c_int64, P]),
-    "fnp_clipcrop_plan": (c_int, [P, c_int, P, P, P, P, c_int, c_int, c_int, P, P, P]),
+    "fnp_bev_bn_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
+    "fnp_bev_bn_train_forward": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, c_float, c_float, P, P, P, P, P,
+                                         P, c_int64, P]),
+    "fnp_bev_bn_train_backward": (c_int, [P, P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, P, P, P, P, P, P, P, P, P, c_int64, P]),
+    "fnp_clipcrop_plan":(c_int, [P, c_int, P, P, P, P, c_int, c_int, c_int, P, P, P]),
     "fnp_clipcrop_sample": (c_int, [P, c_int, c_int, c_int, c_int, P, P, c_int, P, c_int, P, P]),
     "fnp_sparse_to_dense_workspace_bytes": (c_int64, [c_int, c_int, c_int, c_int]),
     "fnp_sparse_to_dense": (c_int, [P, c_int, P, P, c_int, c_int, c_int, c_int, c_int, c_int, P, P, c_int64, P]),

@@ -685,6 +685,38 @@ int fnp_bn_train_backward(const void *grad_out, const void *x, const void *y, in
                           fnp_stream_t stream);
 
 /* ------------------------------------------------------------------------------------------
+ * BatchNorm2d in TRAINING mode + ReLU on rows that stand for a dense map (csrc/bev_bn.hip): the tail of the first
+ * BaseBEVBackbone block (pcdet/models/backbones_2d/base_bev_backbone.py:31-40) behind a bias-free convolution that ran on
+ * sparse rows.  Additive in ABI 14.
+ *   x, grad_x : (cap, C) rows of `dtype` (f32 / bf16 / fp16) on the sites coords (cap, 4) [b, 0, y, x], unique and inside
+ *   the (B, H, W) grid; the n_rows valid rows (DEVICE scalar) are the cells that hold a value, every other of the
+ *   N = B * H * W cells holds 0 and COUNTS in the batch.  y, grad_out: (B, C, H, W) of `dtype`, contiguous.
+ *   gamma, beta, running_*, save_*, fill, grad_gamma, grad_beta: (C,) f32.  C a power of two in [8, 256] whose 64 rows fit
+ *   64 KB of LDS (C = 256: 16-bit rows only); anything else returns FNP_ERR_ARG.
+ *   forward : mean = sum_r x / N, var = sum_r x^2 / N - mean^2 (biased, f64), invstd = 1 / sqrt(var + eps); running
+ *             statistics like torch (momentum, var * N / (N - 1); both may be NULL); num_batches_tracked (nullable) += 1;
+ *             fill_c = relu((0 - mean) * invstd * gamma + beta), the f32 sequence of a row with x = 0;
+ *             y = relu((x - mean) * invstd * gamma + beta) at the row cells, fill_c elsewhere, every element written once.
+ *   backward: g = grad_out * [y > 0] (row cells: y recomputed from x by the forward's f32 sequence and rounded to `dtype`,
+ *             the bits the forward stored; other cells: fill_c > 0);  T = sum over all cells of grad_out, R = over row cells;
+ *             grad_beta = sum_rows g + [fill > 0] (T - R);  grad_gamma = sum_rows g xhat + [fill > 0] xhat_bg (T - R),
+ *             xhat_bg = (0 - mean) * invstd;  grad_x[r] = gamma * invstd * (g_r - grad_beta / N - xhat_r grad_gamma / N)
+ *             for r < n and 0 for n <= r < cap (every row is written).
+ * f64 partial sums added in a fixed order by a finishing launch: no atomics, bit-identical from run to run; no host
+ * synchronisation, no allocation, capturable.  5 launches forward, 6 backward.  workspace: fnp_bev_bn_workspace_bytes()
+ * (cell -> row map + partials), rebuilt by each call.
+ * ------------------------------------------------------------------------------------------ */
+int64_t fnp_bev_bn_workspace_bytes(int C, int B, int H, int W);
+int fnp_bev_bn_train_forward(const void *x, int dtype, const int *coords, const int *n_rows, int cap, int C, int B, int H,
+                             int W, const float *gamma, const float *beta, float *running_mean, float *running_var,
+                             float momentum, float eps, void *y, float *save_mean, float *save_invstd, float *fill,
+                             long long *num_batches_tracked, void *workspace, int64_t workspace_bytes, fnp_stream_t stream);
+int fnp_bev_bn_train_backward(const void *grad_out, const void *x, int dtype, const int *coords, const int *n_rows, int cap,
+                              int C, int B, int H, int W, const float *gamma, const float *beta, const float *save_mean,
+                              const float *save_invstd, const float *fill, void *grad_x, float *grad_gamma, float *grad_beta,
+                              void *workspace, int64_t workspace_bytes, fnp_stream_t stream);
+
+/* ------------------------------------------------------------------------------------------
  * CLIP-crop scoring, geometry half (CLIPBoxClassification.forward,
  * pcdet/models/dense_heads/clip_box_classification.py:230-379): which camera sees which box and the
  * square image crop CLIP looks at.
