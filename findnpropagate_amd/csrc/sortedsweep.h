@@ -3,7 +3,7 @@
 // blockmask for it): spconv_mfma_kernel<..., SORTED> in spconv.hip, its f32-out form, and the LDS-DMA row pipeline of
 // spconv_rows128.hip.
 #pragma once
-#include "common.h"
+#include "conv_launch.h"   // ConvArgs
 
 namespace {
 
@@ -44,6 +44,13 @@ __device__ __forceinline__ void fnp_range_rows(int n, int range, int G, int &row
     row_end = min(n, (int)((nblk16 * (range + 1)) / G) << 4);
 }
 
+// neighbourhood class of a row's 27-bit mask, in sort order: no neighbour in either adjacent z plane, above only (offsets 18..26), both,
+// below only (offsets 0..8)
+__device__ __forceinline__ int fnp_zclass(unsigned m) {
+    const bool lo = (m & 0x1ffu) != 0u, hi = (m & (0x1ffu << 18)) != 0u;
+    return lo ? (hi ? 2 : 3) : (hi ? 1 : 0);
+}
+
 // SORTED work split.  Blocks b and b + 8 share an XCD (and its L2); the slots of one such group own ONE contiguous run of rows
 // [X0, X1) together and take its tiles round-robin: round j = positions [X0 + j S T, X0 + (j + 1) S T), slot s its s-th
 // tile of T rows.  At any time the S workgroups of a group sweep S consecutive tiles — one contiguous region of the
@@ -81,12 +88,8 @@ constexpr int kSortedNW = 8, kSortedMB = 3;
 
 // spconv_rows128.hip: the class-sorted 128 -> 128 sweep, 16-bit in and out, as a double-buffered LDS-DMA row pipeline.  `grid` is the
 // workgroup count perm / blockmask were made for.  Library-internal (not part of the C ABI).
-__attribute__((visibility("hidden"))) int fnp_launch_rows128(int dtype, const void *x, const void *w, const int *nbr, int nbr_stride, const int *n_out,
-                                                             int cap, void *y, const float *scale, const float *shift, const void *residual, int relu,
-                                                             const int *perm, const unsigned *blockmask, int grid, hipStream_t s);
+__attribute__((visibility("hidden"))) int fnp_launch_rows128(int dtype, const ConvArgs &a, const int *perm, const unsigned *blockmask, int grid);
 
 // spconv_out128.hip: a 128 -> 128 convolution of three kernel offsets (conv_out), 16-bit in, 16-bit (out_f32 == 0: the input's type) or f32
 // out, no residual, with the three weight slabs resident in LDS.  Library-internal (not part of the C ABI).
-__attribute__((visibility("hidden"))) int fnp_launch_out128(int in_dtype, int out_f32, const void *x, int x_bytes, const void *w, const int *nbr,
-                                                            int nbr_stride, const int *n_out, int cap, void *y, const float *scale, const float *shift,
-                                                            int relu, hipStream_t s);
+__attribute__((visibility("hidden"))) int fnp_launch_out128(int in_dtype, int out_f32, const ConvArgs &a);

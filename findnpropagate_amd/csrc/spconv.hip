@@ -20,6 +20,7 @@
 // No atomics anywhere: every output row is written once, results are run-to-run identical.
 #include "rankgrid.h"
 #include "sortedsweep.h"   // Vec16, mfma16, SortedRb, the sorted work split
+#include "conv_launch.h"   // ConvArgs, the shared refusals and dispatch idioms
 #include <type_traits>
 
 // Instruments (development builds only, tools/bench_conv.py with FNP_LIB_PATH; the shipped library has neither):
@@ -139,13 +140,12 @@ __global__ __launch_bounds__(256) void spconv_first_kernel(const float *__restri
 }
 
 template <typename TOut>
-int launch_first(const void *x, const void *w, const int *nbr, int nbr_stride, int K, const int *n_out, int cap, void *y,
-                 const float *scale, const float *shift, const void *residual, int relu, int Cin, hipStream_t s) {
-    const int grid = fnp_grid_for(cap, 256, 2048);
-    const size_t lds = sizeof(float) * (size_t)K * Cin * 16;
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(spconv_first_kernel<16, TOut>), dim3(grid), dim3(256), lds, s, (const float *)x,
-                       (const float *)w, nbr, nbr_stride, K, n_out, cap, (TOut *)y, scale, shift, (const TOut *)residual,
-                       relu, Cin);
+int launch_first(const ConvArgs &a, int Cin) {
+    const int grid = fnp_grid_for(a.cap, 256, 2048);
+    const size_t lds = sizeof(float) * (size_t)a.K * Cin * 16;
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spconv_first_kernel<16, TOut>), dim3(grid), dim3(256), lds, a.stream, (const float *)a.x,
+                       (const float *)a.w, a.nbr, a.nbr_stride, a.K, a.n_out, a.cap, (TOut *)a.y, a.scale, a.shift, (const TOut *)a.residual,
+                       a.relu, Cin);
     FNP_LAUNCH_CHECK();
     return FNP_OK;
 }
@@ -1030,56 +1030,55 @@ __global__ __launch_bounds__((NwOf<CIN, COUT, NWO>::value * 64), (MfmaOcc<CIN, C
 #endif
 }
 
-// grid_only: write the workgroup count the launch would use for this capacity and return without launching (the class-sort
-// pass sorts the rows of exactly those ranges)
-template <int CIN, int COUT, int KVOL, bool WIN, typename TOut, bool FUSED = false, typename TAct = __bf16, bool SORTED = false, int NWO = 0>
-int launch_mfma_k(const void *x, int x_bytes, const void *w, const int *nbr, int nbr_stride, int K, const int *n_out, int cap,
-                  void *y, const float *scale, const float *shift, const void *residual, int relu, int hints, hipStream_t s,
-                  const FusedRb *frb_in = nullptr, const SortedRb *srb_in = nullptr, int *grid_only = nullptr, const SplitOut *so_in = nullptr) {
-    constexpr int NWX = NwOf<CIN, COUT, NWO>::value;
-    constexpr int MB = NWO ? MfmaWg<CIN, COUT>::MB_SMALL : MfmaWg<CIN, COUT>::MB;
+// Launch geometry of spconv_mfma_kernel<CIN, COUT, ., KVOL, WIN, TOut, FUSED, ., ., NWO>: plain functions of the capacity, shared by
+// the launch and by the class-sort pass (which sorts the rows of exactly the ranges the sweep's workgroups own)
+template <int CIN, int COUT, int KVOL, bool WIN, typename TOut, bool FUSED = false, int NWO = 0>
+struct MfmaGeom {
     using Cfg = MfmaCfg<CIN, COUT, KVOL>;
-    auto kern = spconv_mfma_kernel<CIN, COUT, MB, KVOL, WIN, TOut, FUSED, TAct, SORTED, NWO>;
-    constexpr int lds = Cfg::lds_bytes(NWX, MB, WIN) + Cfg::epi_bytes(NWX, WIN, sizeof(TOut) == 2) +
-                        (FUSED ? NWX * 27 * MB * 16 * 4 : 0) + COUT * 8;   // (+ BatchNorm scale / shift)
+    static constexpr int NWX = NwOf<CIN, COUT, NWO>::value;
+    static constexpr int MB = NWO ? MfmaWg<CIN, COUT>::MB_SMALL : MfmaWg<CIN, COUT>::MB;
+    static constexpr int lds = Cfg::lds_bytes(NWX, MB, WIN) + Cfg::epi_bytes(NWX, WIN, sizeof(TOut) == 2) +
+                               (FUSED ? NWX * 27 * MB * 16 * 4 : 0) + COUT * 8;   // (+ BatchNorm scale / shift)
+    // workgroups a CU holds: by the register budget (launch bounds), and for the fused-rulebook form by its larger LDS
+    static constexpr int wg_regs = MfmaOcc<CIN, COUT>::WAVES * 4 / NWX;
+    static constexpr int wg_per_cu = lds * wg_regs > 160 * 1024 ? 160 * 1024 / lds : wg_regs;
+    static_assert(wg_per_cu >= 1 && lds * wg_per_cu <= 160 * 1024, "LDS budget of the resident workgroups");
+    static int grid(int cap) {
+        const int tiles = fnp_divup(cap, NWX * MB * 16);
+        // persistent grid: two workgroups per CU are resident (register / LDS budget of the wide
+        // layers); the narrow ALLK layers stage all weights once per workgroup, so keep them few too.
+        // The kernel splits the rows evenly over whatever grid it gets.
+        const int resident = 256 * wg_per_cu;
+        // Small inputs (a single scene: the reference's extraction runs batch size 1): with fewer full tiles than resident
+        // workgroups most CUs would idle while a few sweep MB blocks per wave — split finer instead, down to one 16-site
+        // block per wave (the kernel runs such a range as a partial tile).  The split never changes results.
+        const int fine = fnp_divup(cap, NWX * 16);
+        return tiles >= resident ? resident : (fine < resident ? fine : resident);
+    }
+};
+// grid of the class-sorted 128 -> 128 sweep: perm / blockmask are made for, and every kernel on that order launched with, this
+using SortedGeom = MfmaGeom<128, 128, 27, false, __bf16>;
+
+template <int CIN, int COUT, int KVOL, bool WIN, typename TOut, bool FUSED = false, typename TAct = __bf16, bool SORTED = false, int NWO = 0>
+int launch_mfma_k(const ConvArgs &a, const FusedRb *frb_in = nullptr, const SortedRb *srb_in = nullptr, const SplitOut *so_in = nullptr) {
+    using Geom = MfmaGeom<CIN, COUT, KVOL, WIN, TOut, FUSED, NWO>;
+    auto kern = spconv_mfma_kernel<CIN, COUT, Geom::MB, KVOL, WIN, TOut, FUSED, TAct, SORTED, NWO>;
     FusedRb frb{};
     if (FUSED) {
         if (!frb_in) return FNP_ERR_ARG;
         frb = *frb_in;
     }
     SortedRb srb{nullptr, nullptr};
-    if (SORTED && !grid_only) {
+    if (SORTED) {
         if (!srb_in || !srb_in->perm || !srb_in->blockmask) return FNP_ERR_ARG;
         srb = *srb_in;
     }
-    // workgroups a CU holds: by the register budget (launch bounds), and for the fused-rulebook form by its larger LDS
-    constexpr int wg_regs = MfmaOcc<CIN, COUT>::WAVES * 4 / NWX;
-    constexpr int wg_per_cu = lds * wg_regs > 160 * 1024 ? 160 * 1024 / lds : wg_regs;
-    static_assert(wg_per_cu >= 1 && lds * wg_per_cu <= 160 * 1024, "LDS budget of the resident workgroups");
-    if (lds > 64 * 1024 && !grid_only) {
-        static bool raised = false;  // (idempotent; a race only repeats the call)
-        if (!raised) {
-            if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess)
-                return FNP_ERR_HIP;
-            raised = true;
-        }
+    if (Geom::lds > 64 * 1024) {
+        static bool raised = false;
+        if (const int rc = fnp_raise_lds(reinterpret_cast<const void *>(kern), Geom::lds, raised)) return rc;
     }
-    const int tiles = fnp_divup(cap, NWX * MB * 16);
-    // persistent grid: two workgroups per CU are resident (register / LDS budget of the wide
-    // layers); the narrow ALLK layers stage all weights once per workgroup, so keep them few too.
-    // The kernel splits the rows evenly over whatever grid it gets.
-    const int resident = 256 * wg_per_cu;
-    // Small inputs (a single scene: the reference's extraction runs batch size 1): with fewer full tiles than resident
-    // workgroups most CUs would idle while a few sweep MB blocks per wave — split finer instead, down to one 16-site
-    // block per wave (the kernel runs such a range as a partial tile).  The split never changes results.
-    const int fine = fnp_divup(cap, NWX * 16);
-    const int grid = tiles >= resident ? resident : (fine < resident ? fine : resident);
-    if (grid_only) {
-        *grid_only = grid;
-        return FNP_OK;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(NWX * 64), lds, s, (const TAct *)x, x_bytes, (const TAct *)w,
-                       nbr, nbr_stride, K, n_out, cap, (TOut *)y, scale, shift, (const TOut *)residual, relu, hints, frb, srb,
+    hipLaunchKernelGGL(kern, dim3(Geom::grid(a.cap)), dim3(Geom::NWX * 64), Geom::lds, a.stream, (const TAct *)a.x, (int)a.x_bytes, (const TAct *)a.w,
+                       a.nbr, a.nbr_stride, a.K, a.n_out, a.cap, (TOut *)a.y, a.scale, a.shift, (const TOut *)a.residual, a.relu, a.hints, frb, srb,
                        so_in ? *so_in : SplitOut{nullptr, nullptr, nullptr, 0});
     FNP_LAUNCH_CHECK();
     return FNP_OK;
@@ -1093,36 +1092,26 @@ int launch_mfma_k(const void *x, int x_bytes, const void *w, const int *nbr, int
 template <int CIN, int COUT> struct HasWindow { static constexpr bool value = CIN == 64 && COUT == 64; };
 
 template <int CIN, int COUT, typename TOut, typename TAct>
-int launch_mfma(const void *x, int x_bytes, const void *w, const int *nbr, int nbr_stride, int K, const int *n_out,
-                int cap, void *y, const float *scale, const float *shift, const void *residual, int relu, int hints,
-                hipStream_t s, const SplitOut *so = nullptr) {
-    if (K == 27) {
+int launch_mfma(const ConvArgs &a, const SplitOut *so = nullptr) {
+    if (a.K == 27) {
         if constexpr (HasWindow<CIN, COUT>::value) {
-            if (hints & FNP_HINT_ROWS_RANKED)
-                return launch_mfma_k<CIN, COUT, 27, true, TOut, false, TAct>(x, x_bytes, w, nbr, nbr_stride, K, n_out, cap, y, scale,
-                                                                shift, residual, relu, hints, s, nullptr, nullptr, nullptr, so);
+            if (a.hints & FNP_HINT_ROWS_RANKED) return launch_mfma_k<CIN, COUT, 27, true, TOut, false, TAct>(a, nullptr, nullptr, so);
         }
         if constexpr (CIN == 128 && COUT == 128 && sizeof(TOut) == 2) {
             // fewer rows than the persistent grid has 384-row tiles: the four-wave form (see NwOf)
-            if (cap < 256 * MfmaWg<CIN, COUT>::NW * MfmaWg<CIN, COUT>::MB * 16)
-                return launch_mfma_k<CIN, COUT, 27, false, TOut, false, TAct, false, 4>(x, x_bytes, w, nbr, nbr_stride, K, n_out, cap, y, scale, shift,
-                                                                                        residual, relu, hints, s);
+            if (a.cap < 256 * MfmaWg<CIN, COUT>::NW * MfmaWg<CIN, COUT>::MB * 16) return launch_mfma_k<CIN, COUT, 27, false, TOut, false, TAct, false, 4>(a);
         }
-        return launch_mfma_k<CIN, COUT, 27, false, TOut, false, TAct>(x, x_bytes, w, nbr, nbr_stride, K, n_out, cap, y, scale, shift,
-                                                         residual, relu, hints, s, nullptr, nullptr, nullptr, so);
+        return launch_mfma_k<CIN, COUT, 27, false, TOut, false, TAct>(a, nullptr, nullptr, so);
     }
-    return launch_mfma_k<CIN, COUT, 0, false, TOut, false, TAct>(x, x_bytes, w, nbr, nbr_stride, K, n_out, cap, y, scale, shift, residual,
-                                                    relu, hints, s, nullptr, nullptr, nullptr, so);
+    return launch_mfma_k<CIN, COUT, 0, false, TOut, false, TAct>(a, nullptr, nullptr, so);
 }
 
 template <typename TIn, typename TOut>
-int launch_valu(const void *x, const void *w, const int *nbr, int nbr_stride, int K, const int *n_out, int cap, void *y,
-                const float *scale, const float *shift, const void *residual, int relu, int Cin, int Cout,
-                hipStream_t s) {
-    const int grid = fnp_grid_for((long long)cap * Cout, 256, 256 * 16);
-    hipLaunchKernelGGL(HIP_KERNEL_NAME(spconv_valu_kernel<TIn, TOut>), dim3(grid), dim3(256), 0, s, (const TIn *)x,
-                       (const TIn *)w, nbr, nbr_stride, K, n_out, cap, (TOut *)y, scale, shift, (const TOut *)residual,
-                       relu, Cin, Cout);
+int launch_valu(const ConvArgs &a, int Cin, int Cout) {
+    const int grid = fnp_grid_for((long long)a.cap * Cout, 256, 256 * 16);
+    hipLaunchKernelGGL(HIP_KERNEL_NAME(spconv_valu_kernel<TIn, TOut>), dim3(grid), dim3(256), 0, a.stream, (const TIn *)a.x,
+                       (const TIn *)a.w, a.nbr, a.nbr_stride, a.K, a.n_out, a.cap, (TOut *)a.y, a.scale, a.shift, (const TOut *)a.residual,
+                       a.relu, Cin, Cout);
     FNP_LAUNCH_CHECK();
     return FNP_OK;
 }
@@ -1136,10 +1125,6 @@ int launch_valu(const void *x, const void *w, const int *nbr, int nbr_stride, in
 // row's mask into blockmask[position / 16].  Deterministic: positions depend on the masks only.
 // ------------------------------------------------------------------------------------------
 constexpr int kSortThreads = 1024, kSortQ = 16;   // a thread places at most kSortQ consecutive rows of a round
-__device__ __forceinline__ int fnp_zclass(unsigned m) {
-    const bool lo = (m & 0x1ffu) != 0u, hi = (m & (0x1ffu << 18)) != 0u;
-    return lo ? (hi ? 2 : 3) : (hi ? 1 : 0);
-}
 // per-row masks from the table (for a rulebook that was built without them)
 __global__ __launch_bounds__(256) void rowmask_kernel(const int *__restrict__ nbr, int nbr_stride, const int *__restrict__ n_out, int cap,
                                                       unsigned *__restrict__ rowmask) {
@@ -1226,34 +1211,51 @@ __global__ __launch_bounds__(kSortThreads) void classsort_place_kernel(const uns
 constexpr int kOut128MinCap = FNP_OUT128_MIN_CAP;
 
 template <typename TAct, typename TOut>
-int dispatch_16(const void *x, long long n_in, const void *w, const int *nbr, int nbr_stride, int K, const int *n_out, int cap,
-                  void *y, const float *scale, const float *shift, const void *residual, int relu, int hints, int Cin,
-                  int Cout, hipStream_t s, const SplitOut *so = nullptr) {
-    const long long xb = n_in * Cin * 2;
-    const bool fits = xb > 0 && xb < 0x7fffffffll;   // 32-bit buffer offsets of the MFMA path
+int dispatch_16(const ConvArgs &a, int Cin, int Cout, const SplitOut *so = nullptr) {
+    const bool fits = fnp_fits32(a.x_bytes);   // 32-bit buffer offsets of the MFMA path
     // conv_out (128 -> 128, three offsets, no residual): the kernel with resident slabs and independent waves (spconv_out128.hip),
     // from the capacity at which it is the faster one (kOut128MinCap); same bits as the generic kernel below
-    if (fits && K == 3 && Cin == 128 && Cout == 128 && !residual && !so && cap >= kOut128MinCap)
-        return fnp_launch_out128(std::is_same<TAct, __bf16>::value ? FNP_BF16 : FNP_F16, sizeof(TOut) == 4, x, (int)xb, w, nbr, nbr_stride, n_out, cap, y,
-                                 scale, shift, relu, s);
-#define FNP_CASE(CI, CO)                                                                                       \
-    if (fits && Cin == CI && Cout == CO)                                                                       \
-        return launch_mfma<CI, CO, TOut, TAct>(x, (int)xb, w, nbr, nbr_stride, K, n_out, cap, y, scale, shift, residual,\
-                                         relu, hints, s, so);
-    FNP_CASE(16, 16)
-    FNP_CASE(16, 32)
-    FNP_CASE(32, 32)
-    FNP_CASE(32, 64)
-    FNP_CASE(64, 64)
-    FNP_CASE(64, 128)
-    FNP_CASE(128, 128)
-    // transposed channel pairs: the data gradients of the three channel-doubling convolutions
-    FNP_CASE(32, 16)
-    FNP_CASE(64, 32)
-    FNP_CASE(128, 64)
-#undef FNP_CASE
+    if (fits && a.K == 3 && Cin == 128 && Cout == 128 && !a.residual && !so && a.cap >= kOut128MinCap)
+        return fnp_launch_out128(std::is_same<TAct, __bf16>::value ? FNP_BF16 : FNP_F16, sizeof(TOut) == 4, a);
+    int rc = FNP_ERR_ARG;
+    if (fits && fnp_for_pair(Cin, Cout, rc, ConvPairs{}, [&](auto p) { return launch_mfma<decltype(p)::ci, decltype(p)::co, TOut, TAct>(a, so); })) return rc;
     if (so) return FNP_ERR_ARG;   // (the split outputs are the matrix kernel's)
-    return launch_valu<TAct, TOut>(x, w, nbr, nbr_stride, K, n_out, cap, y, scale, shift, residual, relu, Cin, Cout, s);
+    return launch_valu<TAct, TOut>(a, Cin, Cout);
+}
+
+// the (stride, padding, grid) record of a strided layer whose rulebook the kernel computes itself; false when the geometry is not one it covers
+bool fused_rb(const fnp_rankgrid *in_grid, const fnp_conv_geom *geom, const int *out_coords, FusedRb &frb) {
+    if (!geom || !out_coords || !fnp_rg_valid(in_grid)) return false;
+    for (int d = 0; d < 3; ++d)
+        if (geom->ksize[d] != 3 || geom->stride[d] <= 0 || geom->padding[d] < 0) return false;
+    if (in_grid->D != geom->in_shape[0] || in_grid->H != geom->in_shape[1] || in_grid->W != geom->in_shape[2]) return false;
+    frb.gi = fnp_rg_view(in_grid);
+    for (int d = 0; d < 3; ++d) {
+        frb.s[d] = geom->stride[d];
+        frb.p[d] = geom->padding[d];
+    }
+    frb.out_coords = out_coords;
+    frb.ell_rec = nullptr;
+    frb.ell_cap = 0;
+    return true;
+}
+
+// the 3x3x3 kernel that makes its own rulebook entries (FusedRb), 16-bit in = out, for one of the listed channel pairs
+template <typename Pairs>
+int launch_fused(const ConvArgs &a, int dtype, int Cin, int Cout, const FusedRb &frb, Pairs pairs) {
+    int rc = FNP_ERR_ARG;
+    fnp_for_pair(Cin, Cout, rc, pairs, [&](auto p) {
+        return fnp_dispatch16(dtype, [&](auto t) {
+            using T = typename decltype(t)::type;
+            return launch_mfma_k<decltype(p)::ci, decltype(p)::co, 27, false, T, true, T>(a, &frb);
+        });
+    });
+    return rc;
+}
+
+// what the twin entries of the class-sorted sweep refuse alike
+bool sorted_args_ok(const ConvArgs &a, int n_in_rows, const SortedRb &srb, int Cin, int Cout, bool need_y) {
+    return fnp_conv_args_ok(a, n_in_rows, true, need_y) && srb.perm && srb.blockmask && Cin == 128 && Cout == 128 && fnp_fits32(a.x_bytes);
 }
 
 }  // namespace
@@ -1267,89 +1269,54 @@ extern "C" int fnp_debug_mfma_stamps(unsigned long long *out8) {
 }
 #endif
 
-int fnp_spconv_forward_f32_mfma(const void *feat_in, long long n_in_rows, const void *weight, const int *nbr, int nbr_stride,
-                                int K, const int *n_out, int cap_out, void *feat_out, const float *scale, const float *shift,
-                                const void *residual, int relu, int wperm, int Cin, int Cout, hipStream_t s);   // spconv_f32.hip
+int fnp_spconv_forward_f32_mfma(const ConvArgs &a, int wperm, int Cin, int Cout);   // spconv_f32.hip
 
 extern "C" int fnp_spconv_forward(const void *feat_in, int in_dtype, int n_in_rows, const void *weight, const int *nbr,
                                   int nbr_stride, int K, const int *n_out, int cap_out, void *feat_out, int out_dtype,
                                   const float *scale, const float *shift, const void *residual, int relu, int hints,
                                   int Cin, int Cout, fnp_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!feat_in || !weight || !nbr || !n_out || !feat_out || K <= 0 || Cin <= 0 || Cout <= 0 || cap_out <= 0 ||
-        nbr_stride < cap_out || n_in_rows <= 0)
-        return FNP_ERR_ARG;
-    if ((scale == nullptr) != (shift == nullptr)) return FNP_ERR_ARG;
-    if (in_dtype == FNP_F32 && Cout == 16 && Cin <= 8 && (size_t)K * Cin * 16 * 4 <= 60000) {
-        if (out_dtype == FNP_F32)
-            return launch_first<float>(feat_in, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift,
-                                       residual, relu, Cin, s);
-        if (out_dtype == FNP_BF16)
-            return launch_first<__bf16>(feat_in, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift,
-                                        residual, relu, Cin, s);
-        if (out_dtype == FNP_F16)
-            return launch_first<_Float16>(feat_in, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift,
-                                          residual, relu, Cin, s);
-        return FNP_ERR_ARG;
-    }
+    const ConvArgs a{feat_in, (long long)n_in_rows * Cin * (in_dtype == FNP_F32 ? 4 : 2), weight, nbr, nbr_stride, K, n_out, cap_out, feat_out,
+                     scale, shift, residual, relu, hints, (hipStream_t)stream};
+    if (!fnp_conv_args_ok(a, n_in_rows) || K <= 0 || Cin <= 0 || Cout <= 0) return FNP_ERR_ARG;
     if (in_dtype == FNP_F32) {
+        if (Cout == 16 && Cin <= 8 && (size_t)K * Cin * 16 * 4 <= 60000) {
+            if (out_dtype == FNP_F32) return launch_first<float>(a, Cin);
+            if (out_dtype == FNP_BF16) return launch_first<__bf16>(a, Cin);
+            if (out_dtype == FNP_F16) return launch_first<_Float16>(a, Cin);
+            return FNP_ERR_ARG;
+        }
         if (out_dtype == FNP_F32 && !(hints & FNP_HINT_VALU)) {
             // f32 on the matrix pipe (v_mfma_f32_16x16x4_f32: the same fmaf chain, bit for bit); shapes it does not
             // cover fall through to the thread-per-element chain
-            const int rc = fnp_spconv_forward_f32_mfma(feat_in, n_in_rows, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out,
-                                                       scale, shift, residual, relu, (hints & FNP_HINT_W_PERMUTED) != 0, Cin, Cout, s);
+            const int rc = fnp_spconv_forward_f32_mfma(a, (hints & FNP_HINT_W_PERMUTED) != 0, Cin, Cout);
             if (rc != FNP_ERR_ARG) return rc;
         }
         if (hints & FNP_HINT_W_PERMUTED) return FNP_ERR_ARG;   // the other f32 kernels read the plain layout
-        if (out_dtype == FNP_F32)
-            return launch_valu<float, float>(feat_in, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift,
-                                             residual, relu, Cin, Cout, s);
-        if (out_dtype == FNP_BF16)
-            return launch_valu<float, __bf16>(feat_in, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale,
-                                              shift, residual, relu, Cin, Cout, s);
-        if (out_dtype == FNP_F16)
-            return launch_valu<float, _Float16>(feat_in, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale,
-                                                shift, residual, relu, Cin, Cout, s);
+        if (out_dtype == FNP_F32) return launch_valu<float, float>(a, Cin, Cout);
+        if (out_dtype == FNP_BF16) return launch_valu<float, __bf16>(a, Cin, Cout);
+        if (out_dtype == FNP_F16) return launch_valu<float, _Float16>(a, Cin, Cout);
         return FNP_ERR_ARG;
     }
-    if (in_dtype == FNP_BF16) {
-        if (out_dtype == FNP_BF16)
-            return dispatch_16<__bf16, __bf16>(feat_in, n_in_rows, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift,
-                                               residual, relu, hints, Cin, Cout, s);
-        if (out_dtype == FNP_F32)
-            return dispatch_16<__bf16, float>(feat_in, n_in_rows, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift,
-                                              residual, relu, hints, Cin, Cout, s);
-        return FNP_ERR_ARG;
-    }
-    if (in_dtype == FNP_F16) {   // fp16 features / weights, fp32 accumulate: the reference's AMP mode
-        if (out_dtype == FNP_F16)
-            return dispatch_16<_Float16, _Float16>(feat_in, n_in_rows, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale,
-                                                   shift, residual, relu, hints, Cin, Cout, s);
-        if (out_dtype == FNP_F32)
-            return dispatch_16<_Float16, float>(feat_in, n_in_rows, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift,
-                                                residual, relu, hints, Cin, Cout, s);
-        return FNP_ERR_ARG;
-    }
-    return FNP_ERR_ARG;
+    // bf16, or fp16 features / weights with fp32 accumulate (the reference's AMP mode); out: the input's type or f32
+    return fnp_dispatch16(in_dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        if (out_dtype == in_dtype) return dispatch_16<T, T>(a, Cin, Cout);
+        if (out_dtype == FNP_F32) return dispatch_16<T, float>(a, Cin, Cout);
+        return (int)FNP_ERR_ARG;
+    });
 }
 
 extern "C" int fnp_spconv_forward_split(const void *feat_in, int in_dtype, int n_in_rows, const void *weight, const int *nbr, int nbr_stride,
                                         int K, const int *n_out, int cap_out, float *feat_out, const float *scale, const float *shift,
                                         const float *residual, const void *addend, int relu, int hints, int Cin, int Cout, void *out_hi,
                                         void *out_lo, fnp_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!feat_in || !weight || !nbr || !n_out || !out_hi || !out_lo || K <= 0 || Cin <= 0 || Cout <= 0 || cap_out <= 0 ||
-        nbr_stride < cap_out || n_in_rows <= 0 || (scale == nullptr) != (shift == nullptr))   // (feat_out may be null: only the split is written)
+    const ConvArgs a{feat_in, (long long)n_in_rows * Cin * 2, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift, residual, 0, hints,
+                     (hipStream_t)stream};
+    if (!fnp_conv_args_ok(a, n_in_rows, true, false) || !out_hi || !out_lo || K <= 0 || Cin <= 0 || Cout <= 0)   // (feat_out may be null: only the split is written)
         return FNP_ERR_ARG;
-    if ((((uintptr_t)out_hi | (uintptr_t)out_lo | (uintptr_t)addend) & 7) || ((uintptr_t)feat_out & 15)) return FNP_ERR_ARG;
+    if (!fnp_aligned(7, out_hi, out_lo, addend) || !fnp_aligned(15, feat_out)) return FNP_ERR_ARG;
     const SplitOut so{addend, out_hi, out_lo, relu};
-    if (in_dtype == FNP_BF16)
-        return dispatch_16<__bf16, float>(feat_in, n_in_rows, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift, residual, 0, hints,
-                                          Cin, Cout, s, &so);
-    if (in_dtype == FNP_F16)
-        return dispatch_16<_Float16, float>(feat_in, n_in_rows, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift, residual, 0, hints,
-                                            Cin, Cout, s, &so);
-    return FNP_ERR_ARG;
+    return fnp_dispatch16(in_dtype, [&](auto t) { return dispatch_16<typename decltype(t)::type, float>(a, Cin, Cout, &so); });
 }
 
 // Strided 3x3x3 convolution with its rulebook computed inside the kernel (see FusedRb): for a layer whose rulebook
@@ -1359,39 +1326,12 @@ extern "C" int fnp_spconv_forward_strided(const void *feat_in, int in_dtype, int
                                           const fnp_rankgrid *in_grid, const fnp_conv_geom *geom, const int *out_coords,
                                           const int *n_out, int cap_out, void *feat_out, int out_dtype, const float *scale,
                                           const float *shift, int relu, int Cin, int Cout, fnp_stream_t stream) {
-    hipStream_t s = (hipStream_t)stream;
-    if (!feat_in || !weight || !geom || !out_coords || !n_out || !feat_out || cap_out <= 0 || n_in_rows <= 0 ||
-        !fnp_rg_valid(in_grid))
-        return FNP_ERR_ARG;
-    if ((scale == nullptr) != (shift == nullptr)) return FNP_ERR_ARG;
-    if ((in_dtype != FNP_BF16 && in_dtype != FNP_F16) || out_dtype != in_dtype) return FNP_ERR_ARG;
-    for (int d = 0; d < 3; ++d)
-        if (geom->ksize[d] != 3 || geom->stride[d] <= 0 || geom->padding[d] < 0) return FNP_ERR_ARG;
-    if (in_grid->D != geom->in_shape[0] || in_grid->H != geom->in_shape[1] || in_grid->W != geom->in_shape[2]) return FNP_ERR_ARG;
-    const long long xb = (long long)n_in_rows * Cin * 2;
-    if (xb <= 0 || xb >= 0x7fffffffll) return FNP_ERR_ARG;
+    const ConvArgs a{feat_in, (long long)n_in_rows * Cin * 2, weight, nullptr, cap_out, 27, n_out, cap_out, feat_out, scale, shift, nullptr, relu, 0,
+                     (hipStream_t)stream};
     FusedRb frb;
-    frb.gi = fnp_rg_view(in_grid);
-    for (int d = 0; d < 3; ++d) {
-        frb.s[d] = geom->stride[d];
-        frb.p[d] = geom->padding[d];
-    }
-    frb.out_coords = out_coords;
-    frb.ell_rec = nullptr;
-    frb.ell_cap = 0;
-#define FNP_FCASE(CI, CO)                                                                                                   \
-    if (Cin == CI && Cout == CO) {                                                                                          \
-        if (in_dtype == FNP_F16)                                                                                            \
-            return launch_mfma_k<CI, CO, 27, false, _Float16, true, _Float16>(feat_in, (int)xb, weight, nullptr, cap_out, 27, n_out, \
-                                                                              cap_out, feat_out, scale, shift, nullptr, relu, 0, s, &frb); \
-        return launch_mfma_k<CI, CO, 27, false, __bf16, true>(feat_in, (int)xb, weight, nullptr, cap_out, 27, n_out, cap_out, feat_out, \
-                                                              scale, shift, nullptr, relu, 0, s, &frb);                     \
-    }
-    FNP_FCASE(16, 32)
-    FNP_FCASE(32, 64)
-    FNP_FCASE(64, 128)
-#undef FNP_FCASE
-    return FNP_ERR_ARG;
+    if (!fnp_conv_args_ok(a, n_in_rows, false) || out_dtype != in_dtype || !fnp_fits32(a.x_bytes) || !fused_rb(in_grid, geom, out_coords, frb))
+        return FNP_ERR_ARG;
+    return launch_fused(a, in_dtype, Cin, Cout, frb, PairList<ChPair<16, 32>, ChPair<32, 64>, ChPair<64, 128>>{});
 }
 
 // The 16-channel layers on the COMPACT rulebook, on the matrix pipe (see FusedRb): fnp_spconv_forward_ell's arguments for
@@ -1399,27 +1339,14 @@ extern "C" int fnp_spconv_forward_strided(const void *feat_in, int in_dtype, int
 extern "C" int fnp_spconv_forward_ell_mfma(const void *feat_in, int in_dtype, int n_in_rows, const void *weight, const void *records, int cap_rows,
                                            int pool_records, const int *n_out, void *feat_out, int out_dtype, const float *scale, const float *shift,
                                            const void *residual, int relu, int Cin, int Cout, fnp_stream_t stream) {
-    if (!feat_in || !weight || !records || !n_out || !feat_out || cap_rows <= 0 || pool_records < 0 || n_in_rows <= 0) return FNP_ERR_ARG;
-    if ((scale == nullptr) != (shift == nullptr) || ((uintptr_t)records & 15)) return FNP_ERR_ARG;
-    if ((in_dtype != FNP_BF16 && in_dtype != FNP_F16) || out_dtype != in_dtype || Cin != 16 || (Cout != 16 && Cout != 32)) return FNP_ERR_ARG;
-    const long long xb = (long long)n_in_rows * Cin * 2;
-    if (xb >= 0x7fffffffll || (long long)cap_rows + pool_records >= (1ll << 26) || n_in_rows >= (1 << 27)) return FNP_ERR_ARG;
+    const ConvArgs a{feat_in, (long long)n_in_rows * Cin * 2, weight, nullptr, cap_rows, 27, n_out, cap_rows, feat_out, scale, shift, residual, relu, 0,
+                     (hipStream_t)stream};
+    if (!fnp_conv_args_ok(a, n_in_rows, false) || !records || pool_records < 0 || !fnp_aligned(15, records) || out_dtype != in_dtype) return FNP_ERR_ARG;
+    if (!fnp_fits32(a.x_bytes) || (long long)cap_rows + pool_records >= (1ll << 26) || n_in_rows >= (1 << 27)) return FNP_ERR_ARG;
     FusedRb frb{};
     frb.ell_rec = (const unsigned *)records;
     frb.ell_cap = cap_rows;
-    hipStream_t s = (hipStream_t)stream;
-#define FNP_ECASE(CO)                                                                                                                         \
-    if (Cout == CO) {                                                                                                                         \
-        if (in_dtype == FNP_F16)                                                                                                              \
-            return launch_mfma_k<16, CO, 27, false, _Float16, true, _Float16>(feat_in, (int)xb, weight, nullptr, cap_rows, 27, n_out, cap_rows, \
-                                                                              feat_out, scale, shift, residual, relu, 0, s, &frb);            \
-        return launch_mfma_k<16, CO, 27, false, __bf16, true>(feat_in, (int)xb, weight, nullptr, cap_rows, 27, n_out, cap_rows, feat_out,     \
-                                                              scale, shift, residual, relu, 0, s, &frb);                                      \
-    }
-    FNP_ECASE(16)
-    FNP_ECASE(32)
-#undef FNP_ECASE
-    return FNP_ERR_ARG;
+    return launch_fused(a, in_dtype, Cin, Cout, frb, PairList<ChPair<16, 16>, ChPair<16, 32>>{});
 }
 
 
@@ -1446,11 +1373,8 @@ extern "C" int fnp_rulebook_classsort(const int *nbr, int nbr_stride, int K, con
         FNP_LAUNCH_CHECK();
         rowmask = (const unsigned *)workspace;
     }
-    int grid = 0;
-    const int rc = launch_mfma_k<128, 128, 27, false, __bf16, false, __bf16, true>(nullptr, 0, nullptr, nullptr, cap_out, 27, n_out, cap_out, nullptr, nullptr,
-                                                                                    nullptr, nullptr, 0, 0, s, nullptr, nullptr, &grid);
-    if (rc != FNP_OK) return rc;
-    constexpr int NW = MfmaWg<128, 128>::NW, TILE = NW * MfmaWg<128, 128>::MB * 16;
+    const int grid = SortedGeom::grid(cap_out);
+    constexpr int NW = SortedGeom::NWX, TILE = NW * SortedGeom::MB * 16;
     const int slots = (grid >> 3) + ((grid & 7) ? 1 : 0);
     if ((long long)slots * TILE > (long long)kSortThreads * kSortQ) return FNP_ERR_ARG;   // (a round is placed by one workgroup)
     const int rounds = fnp_divup(fnp_divup(cap_out, 8) + 16 * (slots + 1), (long long)((grid >> 3) > 0 ? (grid >> 3) : 1) * TILE) + 1;
@@ -1464,60 +1388,38 @@ extern "C" int fnp_spconv_forward_sorted(const void *feat_in, int dtype, int n_i
                                          const int *perm, const unsigned *blockmask, const int *n_out, int cap_out, void *feat_out,
                                          const float *scale, const float *shift, const void *residual, int relu, int Cin, int Cout,
                                          fnp_stream_t stream) {
-    if (!feat_in || !weight || !nbr || !perm || !blockmask || !n_out || !feat_out || cap_out <= 0 || nbr_stride < cap_out || n_in_rows <= 0)
-        return FNP_ERR_ARG;
-    if ((scale == nullptr) != (shift == nullptr) || Cin != 128 || Cout != 128) return FNP_ERR_ARG;
-    const long long xb = (long long)n_in_rows * Cin * 2;
-    if (xb >= 0x7fffffffll) return FNP_ERR_ARG;
+    const ConvArgs a{feat_in, (long long)n_in_rows * Cin * 2, weight, nbr, nbr_stride, 27, n_out, cap_out, feat_out, scale, shift, residual, relu, 0,
+                     (hipStream_t)stream};
     const SortedRb srb{perm, blockmask};
+    if (!sorted_args_ok(a, n_in_rows, srb, Cin, Cout, true)) return FNP_ERR_ARG;
     // Launches that give every wave of the persistent grid at least one 16-row block take the LDS-DMA row pipeline of
     // spconv_rows128.hip — the same tiles, rounds and sums (bit-identical); fewer rows (the one-scene path: a few thousand
     // rows, part of the grid idle and the time in the slab stream, not the gathers) stay on the register pipeline below.
-    static_assert(MfmaWg<128, 128>::NW == kSortedNW && MfmaWg<128, 128>::MB == kSortedMB && MfmaOcc<128, 128>::WAVES == 2,
+    static_assert(SortedGeom::NWX == kSortedNW && SortedGeom::MB == kSortedMB && MfmaOcc<128, 128>::WAVES == 2,
                   "the row pipeline sweeps the sorted grid's tiles: its geometry is the one sortedsweep.h names");
-    if ((dtype == FNP_BF16 || dtype == FNP_F16) && cap_out >= 256 * kSortedNW * 16) {
-        int grid = 0;
-        const int rc = launch_mfma_k<128, 128, 27, false, __bf16, false, __bf16, true>(nullptr, 0, nullptr, nullptr, cap_out, 27, n_out, cap_out, nullptr,
-                                                                                        nullptr, nullptr, nullptr, 0, 0, (hipStream_t)stream, nullptr, nullptr, &grid);
-        if (rc != FNP_OK) return rc;
-        return fnp_launch_rows128(dtype, feat_in, weight, nbr, nbr_stride, n_out, cap_out, feat_out, scale, shift, residual, relu, perm, blockmask, grid,
-                                  (hipStream_t)stream);
-    }
-    if (dtype == FNP_BF16)
-        return launch_mfma_k<128, 128, 27, false, __bf16, false, __bf16, true>(feat_in, (int)xb, weight, nbr, nbr_stride, 27, n_out, cap_out, feat_out, scale,
-                                                                                shift, residual, relu, 0, (hipStream_t)stream, nullptr, &srb);
-    if (dtype == FNP_F16)
-        return launch_mfma_k<128, 128, 27, false, _Float16, false, _Float16, true>(feat_in, (int)xb, weight, nbr, nbr_stride, 27, n_out, cap_out, feat_out,
-                                                                                    scale, shift, residual, relu, 0, (hipStream_t)stream, nullptr, &srb);
-    return FNP_ERR_ARG;
+    if ((dtype == FNP_BF16 || dtype == FNP_F16) && cap_out >= 256 * kSortedNW * 16) return fnp_launch_rows128(dtype, a, perm, blockmask, SortedGeom::grid(cap_out));
+    return fnp_dispatch16(dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return launch_mfma_k<128, 128, 27, false, T, false, T, true>(a, nullptr, &srb);
+    });
 }
 
 extern "C" int fnp_spconv_forward_sorted_split(const void *feat_in, int dtype, int n_in_rows, const void *weight, const int *nbr, int nbr_stride,
                                                const int *perm, const unsigned *blockmask, const int *n_out, int cap_out, float *feat_out,
                                                const float *scale, const float *shift, const float *residual, const void *addend, int relu,
                                                int Cin, int Cout, void *out_hi, void *out_lo, fnp_stream_t stream) {
-    if (!feat_in || !weight || !nbr || !perm || !blockmask || !n_out || !out_hi || !out_lo || cap_out <= 0 || nbr_stride < cap_out || n_in_rows <= 0)
-        return FNP_ERR_ARG;
-    if ((scale == nullptr) != (shift == nullptr) || Cin != 128 || Cout != 128) return FNP_ERR_ARG;
-    if ((((uintptr_t)out_hi | (uintptr_t)out_lo | (uintptr_t)addend) & 7) || ((uintptr_t)feat_out & 15)) return FNP_ERR_ARG;
-    const long long xb = (long long)n_in_rows * Cin * 2;
-    if (xb >= 0x7fffffffll) return FNP_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
+    const ConvArgs a{feat_in, (long long)n_in_rows * Cin * 2, weight, nbr, nbr_stride, 27, n_out, cap_out, feat_out, scale, shift, residual, 0, 0,
+                     (hipStream_t)stream};
+    const SortedRb srb{perm, blockmask};
+    if (!sorted_args_ok(a, n_in_rows, srb, Cin, Cout, false) || !out_hi || !out_lo) return FNP_ERR_ARG;
+    if (!fnp_aligned(7, out_hi, out_lo, addend) || !fnp_aligned(15, feat_out)) return FNP_ERR_ARG;
     // perm / blockmask were made for the workgroup ranges of the 16-bit-output sweep (fnp_rulebook_classsort): this launch must cut
     // the rows the same way
-    int g16 = 0, g32 = 0;
-    launch_mfma_k<128, 128, 27, false, __bf16, false, __bf16, true>(nullptr, 0, nullptr, nullptr, cap_out, 27, n_out, cap_out, nullptr, nullptr, nullptr, nullptr,
-                                                                    0, 0, s, nullptr, nullptr, &g16);
-    launch_mfma_k<128, 128, 27, false, float, false, __bf16, true>(nullptr, 0, nullptr, nullptr, cap_out, 27, n_out, cap_out, nullptr, nullptr, nullptr, nullptr,
-                                                                   0, 0, s, nullptr, nullptr, &g32);
-    if (g16 != g32) return FNP_ERR_ARG;
-    const SortedRb srb{perm, blockmask};
+    using Geom32 = MfmaGeom<128, 128, 27, false, float>;
+    static_assert(Geom32::NWX == SortedGeom::NWX && Geom32::MB == SortedGeom::MB && Geom32::wg_per_cu == SortedGeom::wg_per_cu,
+                  "the f32-output sweep has the grid of the 16-bit one at every capacity");
     const SplitOut so{addend, out_hi, out_lo, relu};
-    if (dtype == FNP_BF16)
-        return launch_mfma_k<128, 128, 27, false, float, false, __bf16, true>(feat_in, (int)xb, weight, nbr, nbr_stride, 27, n_out, cap_out, feat_out, scale, shift,
-                                                                              residual, 0, 0, s, nullptr, &srb, nullptr, &so);
-    if (dtype == FNP_F16)
-        return launch_mfma_k<128, 128, 27, false, float, false, _Float16, true>(feat_in, (int)xb, weight, nbr, nbr_stride, 27, n_out, cap_out, feat_out, scale,
-                                                                                shift, residual, 0, 0, s, nullptr, &srb, nullptr, &so);
-    return FNP_ERR_ARG;
+    return fnp_dispatch16(dtype, [&](auto t) {
+        return launch_mfma_k<128, 128, 27, false, float, false, typename decltype(t)::type, true>(a, nullptr, &srb, &so);
+    });
 }

@@ -22,6 +22,7 @@
 // BatchNorm(eval) scale / shift, residual and ReLU in the epilogue, as in spconv_mfma_kernel.  No atomics in the sum:
 // run-to-run identical.
 #include "rankgrid.h"
+#include "conv_launch.h"   // ConvArgs, the shared refusals and dispatch idioms
 #include <type_traits>
 
 namespace {
@@ -315,18 +316,17 @@ __global__ __launch_bounds__(kThreads) void spconv_ell_kernel(const TIn *__restr
 }
 
 template <int CIN, int COUT, typename TIn, typename TOut>
-int launch_ell(const void *x, long long x_bytes, const void *w, const unsigned *rec, long long rec_records, const int *n_out, int cap, void *y,
-               const float *scale, const float *shift, const void *residual, int relu, hipStream_t s) {
+int launch_ell(const ConvArgs &a, const unsigned *rec, long long rec_records) {
     using W = EllW<CIN, std::is_same<TIn, float>::value>;
     constexpr int lds = 27 * (COUT / 4) * W::NQP * 16;
     constexpr int RPB = (64 / (COUT / 4)) * (kThreads / 64);
     auto kern = spconv_ell_kernel<CIN, COUT, TIn, TOut>;
     // up to 8 workgroups per CU (64 VGPRs), fewer where the weight image is large
     const int per_cu = lds * 8 <= 160 * 1024 ? 8 : (160 * 1024) / lds;
-    const int grid = fnp_grid_for(cap, RPB, 256 * per_cu);
+    const int grid = fnp_grid_for(a.cap, RPB, 256 * per_cu);
     const unsigned char *perm = reinterpret_cast<const unsigned char *>(rec) + (size_t)rec_records * 32;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, s, (const TIn *)x, (int)x_bytes, (const TIn *)w, rec, (int)rec_records, perm, n_out, cap,
-                       (TOut *)y, scale, shift, (const TOut *)residual, relu);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kThreads), lds, a.stream, (const TIn *)a.x, (int)a.x_bytes, (const TIn *)a.w, rec, (int)rec_records, perm, a.n_out,
+                       a.cap, (TOut *)a.y, a.scale, a.shift, (const TOut *)a.residual, a.relu);
     FNP_LAUNCH_CHECK();
     return FNP_OK;
 }
@@ -373,37 +373,22 @@ extern "C" int fnp_rulebook_ell(const int *coords, const int *n_rows, int cap, c
 extern "C" int fnp_spconv_forward_ell(const void *feat_in, int in_dtype, int n_in_rows, const void *weight, const void *records, int cap_rows,
                                       int pool_records, const int *n_out, void *feat_out, int out_dtype, const float *scale, const float *shift,
                                       const void *residual, int relu, int Cin, int Cout, fnp_stream_t stream) {
-    if (!feat_in || !weight || !records || !n_out || !feat_out || cap_rows <= 0 || pool_records < 0 || n_in_rows <= 0) return FNP_ERR_ARG;
-    if ((scale == nullptr) != (shift == nullptr)) return FNP_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
+    const ConvArgs a{feat_in, (long long)n_in_rows * Cin * (in_dtype == FNP_F32 ? 4 : 2), weight, nullptr, cap_rows, 27, n_out, cap_rows, feat_out, scale, shift,
+                     residual, relu, 0, (hipStream_t)stream};
+    if (!fnp_conv_args_ok(a, n_in_rows, false) || !records || pool_records < 0) return FNP_ERR_ARG;
     const unsigned *rec = (const unsigned *)records;
     const long long nrec = (long long)cap_rows + pool_records;
-    if (nrec >= (1ll << 26) || n_in_rows >= (1 << 27)) return FNP_ERR_ARG;
-    if (in_dtype == FNP_F32) {
-        const long long xb = (long long)n_in_rows * Cin * 4;
-        if (Cout != 16 || xb >= 0x7fffffffll) return FNP_ERR_ARG;
-#define FNP_ELL_FIRST(CI)                                                                                                                   \
-    if (Cin == CI) {                                                                                                                        \
-        if (out_dtype == FNP_F32) return launch_ell<CI, 16, float, float>(feat_in, xb, weight, rec, nrec, n_out, cap_rows, feat_out, scale, shift, residual, relu, s); \
-        if (out_dtype == FNP_BF16) return launch_ell<CI, 16, float, __bf16>(feat_in, xb, weight, rec, nrec, n_out, cap_rows, feat_out, scale, shift, residual, relu, s); \
-        if (out_dtype == FNP_F16) return launch_ell<CI, 16, float, _Float16>(feat_in, xb, weight, rec, nrec, n_out, cap_rows, feat_out, scale, shift, residual, relu, s); \
-        return FNP_ERR_ARG;                                                                                                                 \
-    }
-        FNP_ELL_FIRST(4)
-        FNP_ELL_FIRST(5)
-#undef FNP_ELL_FIRST
+    if (nrec >= (1ll << 26) || n_in_rows >= (1 << 27) || !fnp_fits32(a.x_bytes)) return FNP_ERR_ARG;
+    if (in_dtype == FNP_F32) {   // the first layer: 4 or 5 point features -> 16 channels of any type
+        if (Cout != 16 || (Cin != 4 && Cin != 5)) return FNP_ERR_ARG;
+        if (out_dtype == FNP_F32) return Cin == 4 ? launch_ell<4, 16, float, float>(a, rec, nrec) : launch_ell<5, 16, float, float>(a, rec, nrec);
+        if (out_dtype == FNP_BF16) return Cin == 4 ? launch_ell<4, 16, float, __bf16>(a, rec, nrec) : launch_ell<5, 16, float, __bf16>(a, rec, nrec);
+        if (out_dtype == FNP_F16) return Cin == 4 ? launch_ell<4, 16, float, _Float16>(a, rec, nrec) : launch_ell<5, 16, float, _Float16>(a, rec, nrec);
         return FNP_ERR_ARG;
     }
-    if ((in_dtype != FNP_BF16 && in_dtype != FNP_F16) || out_dtype != in_dtype || Cin != 16) return FNP_ERR_ARG;
-    const long long xb = (long long)n_in_rows * Cin * 2;
-    if (xb >= 0x7fffffffll) return FNP_ERR_ARG;
-    if (Cout == 16) {
-        if (in_dtype == FNP_BF16) return launch_ell<16, 16, __bf16, __bf16>(feat_in, xb, weight, rec, nrec, n_out, cap_rows, feat_out, scale, shift, residual, relu, s);
-        return launch_ell<16, 16, _Float16, _Float16>(feat_in, xb, weight, rec, nrec, n_out, cap_rows, feat_out, scale, shift, residual, relu, s);
-    }
-    if (Cout == 32) {
-        if (in_dtype == FNP_BF16) return launch_ell<16, 32, __bf16, __bf16>(feat_in, xb, weight, rec, nrec, n_out, cap_rows, feat_out, scale, shift, residual, relu, s);
-        return launch_ell<16, 32, _Float16, _Float16>(feat_in, xb, weight, rec, nrec, n_out, cap_rows, feat_out, scale, shift, residual, relu, s);
-    }
-    return FNP_ERR_ARG;
+    if (out_dtype != in_dtype || Cin != 16 || (Cout != 16 && Cout != 32)) return FNP_ERR_ARG;
+    return fnp_dispatch16(in_dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return Cout == 16 ? launch_ell<16, 16, T, T>(a, rec, nrec) : launch_ell<16, 32, T, T>(a, rec, nrec);
+    });
 }

@@ -18,12 +18,9 @@
 // current one (64 MFMAs = 2,048 cycles per wave at 128 output channels), rulebook entries two offsets ahead.
 // A 16-site block none of whose sites has a neighbour at an offset skips that offset's MFMAs (wave-uniform branch;
 // 44-68 % of the (block, offset) pairs in the stage-1 layers): fmaf(0, w, acc) == acc, the chains are unchanged.
-#include "common.h"
+#include "sortedsweep.h"   // f32x4, u32x4, fnp_zclass, fnp_range_rows; conv_launch.h
 
 namespace {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // 4x4 transpose of (lane row q, register r) inside every 16-lane column group: out[r] of lane row q = in[q] of lane row r
 __device__ __forceinline__ void transpose4(u32x4 &v) {
@@ -235,42 +232,27 @@ __global__ __launch_bounds__(256, (F32Occ<COUT>::WAVES)) void spconv_mfma_f32_ke
     }
 }
 
-template <int CIN, int COUT>
-int launch_f32(const void *x, long long x_bytes, const void *w, const int *nbr, int nbr_stride, int K, const int *n_out, int cap,
-               void *y, const float *scale, const float *shift, const void *residual, int relu, bool wperm, hipStream_t s,
-               const int *perm = nullptr, int *grid_only = nullptr) {
-    // sites per wave: 4 blocks up to 64 output channels (a weight fragment then serves 64 sites), 3 for 128
-    // (accumulators = COUT/16 * MB * 4 registers; measured on MI355X at 64 scenes: 128 -> 128 4.54 -> 4.30 ms with 3
-    // instead of 2, 64 -> 64 2.96 -> 2.68 ms with 4 instead of 2)
-    constexpr int MB = COUT <= 64 ? 4 : 3;
-    const int tiles = fnp_divup(cap, 4 * MB * 16);
+// sites per wave: 4 blocks up to 64 output channels (a weight fragment then serves 64 sites), 3 for 128
+// (accumulators = COUT/16 * MB * 4 registers; measured on MI355X at 64 scenes: 128 -> 128 4.54 -> 4.30 ms with 3
+// instead of 2, 64 -> 64 2.96 -> 2.68 ms with 4 instead of 2)
+template <int COUT> constexpr int kF32MB = COUT <= 64 ? 4 : 3;
+// grid of the f32 kernel at COUT output channels: the launch's, and the one fnp_rulebook_classsort_f32 sorts the ranges of
+template <int COUT> int f32_grid(int cap) {
+    const int tiles = fnp_divup(cap, 4 * kF32MB<COUT> * 16);
     const int resident = 256 * F32Occ<COUT>::WAVES;      // one 4-wave workgroup per CU and wave slot
     const int fine = fnp_divup(cap, 4 * 16);            // small inputs: down to one 16-site block per wave
-    const int grid = tiles >= resident ? resident : (fine < resident ? fine : resident);
-    if (grid_only) {
-        *grid_only = grid;
-        return FNP_OK;
-    }
-    if (perm) {
-        if (wperm)
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(spconv_mfma_f32_kernel<CIN, COUT, MB, true, true>), dim3(grid), dim3(256), 0, s,
-                               (const float *)x, (int)x_bytes, (const float *)w, nbr, nbr_stride, K, n_out, cap, (float *)y, scale,
-                               shift, (const float *)residual, relu, perm);
-        else
-            hipLaunchKernelGGL(HIP_KERNEL_NAME(spconv_mfma_f32_kernel<CIN, COUT, MB, false, true>), dim3(grid), dim3(256), 0, s,
-                               (const float *)x, (int)x_bytes, (const float *)w, nbr, nbr_stride, K, n_out, cap, (float *)y, scale,
-                               shift, (const float *)residual, relu, perm);
-        FNP_LAUNCH_CHECK();
-        return FNP_OK;
-    }
-    if (wperm)
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(spconv_mfma_f32_kernel<CIN, COUT, MB, true>), dim3(grid), dim3(256), 0, s,
-                           (const float *)x, (int)x_bytes, (const float *)w, nbr, nbr_stride, K, n_out, cap, (float *)y, scale,
-                           shift, (const float *)residual, relu);
-    else
-        hipLaunchKernelGGL(HIP_KERNEL_NAME(spconv_mfma_f32_kernel<CIN, COUT, MB, false>), dim3(grid), dim3(256), 0, s,
-                           (const float *)x, (int)x_bytes, (const float *)w, nbr, nbr_stride, K, n_out, cap, (float *)y, scale,
-                           shift, (const float *)residual, relu);
+    return tiles >= resident ? resident : (fine < resident ? fine : resident);
+}
+
+template <int CIN, int COUT>
+int launch_f32(const ConvArgs &a, bool wperm, const int *perm = nullptr) {
+    constexpr int MB = kF32MB<COUT>;
+    // [rows in class-sorted order][weights 4 x 4-transposed]
+    void (*const kern[2][2])(const float *, int, const float *, const int *, int, int, const int *, int, float *, const float *, const float *, const float *,
+                             int, const int *) = {{spconv_mfma_f32_kernel<CIN, COUT, MB, false>, spconv_mfma_f32_kernel<CIN, COUT, MB, true>},
+                                                  {spconv_mfma_f32_kernel<CIN, COUT, MB, false, true>, spconv_mfma_f32_kernel<CIN, COUT, MB, true, true>}};
+    hipLaunchKernelGGL(kern[perm != nullptr][wperm], dim3(f32_grid<COUT>(a.cap)), dim3(256), 0, a.stream, (const float *)a.x, (int)a.x_bytes,
+                       (const float *)a.w, a.nbr, a.nbr_stride, a.K, a.n_out, a.cap, (float *)a.y, a.scale, a.shift, (const float *)a.residual, a.relu, perm);
     FNP_LAUNCH_CHECK();
     return FNP_OK;
 }
@@ -280,10 +262,6 @@ int launch_f32(const void *x, long long x_bytes, const void *w, const int *nbr, 
 // position per class, and it places its rows in order (stable: rows of a class keep their order).  A range of more than
 // 16,384 rows keeps its own order.
 constexpr int kF32SortThreads = 1024, kF32SortQ = 16;
-__device__ __forceinline__ int f32_zclass(unsigned m) {
-    const bool lo = (m & 0x1ffu) != 0u, hi = (m & (0x1ffu << 18)) != 0u;
-    return lo ? (hi ? 2 : 3) : (hi ? 1 : 0);
-}
 __global__ __launch_bounds__(kF32SortThreads) void f32_classsort_kernel(const unsigned *__restrict__ rowmask, const int *__restrict__ n_out, int cap,
                                                                         int *__restrict__ perm) {
     constexpr int NWV = kF32SortThreads / 64;
@@ -292,8 +270,8 @@ __global__ __launch_bounds__(kF32SortThreads) void f32_classsort_kernel(const un
     const int G = gridDim.x;
     const int xcd = blockIdx.x & 7, slot = blockIdx.x >> 3, per = G >> 3, rem = G & 7;
     const int range = (xcd < rem ? xcd * (per + 1) : rem * (per + 1) + (xcd - rem) * per) + slot;
-    const long long nblk16 = (n + 15) >> 4;
-    const int b = (int)((nblk16 * range) / G) << 4, e = min(n, (int)((nblk16 * (range + 1)) / G) << 4);
+    int b, e;
+    fnp_range_rows(n, range, G, b, e);
     if (b >= e) return;
     if (e - b > kF32SortThreads * kF32SortQ) {   // (uniform) too long for one workgroup: row order
         for (int r = b + tid; r < e; r += kF32SortThreads) perm[r] = r;
@@ -307,7 +285,7 @@ __global__ __launch_bounds__(kF32SortThreads) void f32_classsort_kernel(const un
         m[u] = 0u;
         if (u < q && r0 + u < e) {
             m[u] = rowmask[r0 + u];
-            cnt += 1ull << (16 * f32_zclass(m[u]));
+            cnt += 1ull << (16 * fnp_zclass(m[u]));
         }
     }
     unsigned long long v = cnt;
@@ -335,79 +313,44 @@ __global__ __launch_bounds__(kF32SortThreads) void f32_classsort_kernel(const un
 #pragma unroll
     for (int u = 0; u < kF32SortQ; ++u) {
         if (u < q && r0 + u < e) {
-            const int c = f32_zclass(m[u]);
+            const int c = fnp_zclass(m[u]);
             perm[b + (c == 0 ? run[0]++ : c == 1 ? run[1]++ : c == 2 ? run[2]++ : run[3]++)] = r0 + u;
         }
     }
 }
 
-}  // namespace
+// the layers that have a class-sorted form
+using F32SortedPairs = PairList<ChPair<16, 16>, ChPair<32, 32>, ChPair<64, 64>, ChPair<128, 128>>;
 
-template <int CIN, int COUT> static int f32_grid(int cap, int *grid) {
-    return launch_f32<CIN, COUT>(nullptr, 0, nullptr, nullptr, cap, 27, nullptr, cap, nullptr, nullptr, nullptr, nullptr, 0, false, nullptr, nullptr, grid);
-}
+}  // namespace
 
 // perm (cap_out) int32 for fnp_spconv_forward_f32_sorted of this (Cin, Cout): valid for the (rowmask, n_out, cap_out) it was made from
 extern "C" int fnp_rulebook_classsort_f32(const unsigned *rowmask, const int *n_out, int cap_out, int Cin, int Cout, int *perm, fnp_stream_t stream) {
     if (!rowmask || !n_out || !perm || cap_out <= 0) return FNP_ERR_ARG;
-    int grid = 0, rc = FNP_ERR_ARG;
-#define FNP_GCASE(CI, CO) if (Cin == CI && Cout == CO) rc = f32_grid<CI, CO>(cap_out, &grid);
-    FNP_GCASE(16, 16)
-    FNP_GCASE(32, 32)
-    FNP_GCASE(64, 64)
-    FNP_GCASE(128, 128)
-#undef FNP_GCASE
-    if (rc != FNP_OK) return rc;
+    int grid = 0;
+    if (!fnp_for_pair(Cin, Cout, grid, F32SortedPairs{}, [&](auto p) { return f32_grid<decltype(p)::co>(cap_out); })) return FNP_ERR_ARG;
     hipLaunchKernelGGL(f32_classsort_kernel, dim3(grid), dim3(kF32SortThreads), 0, (hipStream_t)stream, rowmask, n_out, cap_out, perm);
     FNP_LAUNCH_CHECK();
     return FNP_OK;
 }
 
-int fnp_spconv_forward_f32_mfma(const void *feat_in, long long n_in_rows, const void *weight, const int *nbr, int nbr_stride,
-                                int K, const int *n_out, int cap_out, void *feat_out, const float *scale, const float *shift,
-                                const void *residual, int relu, int wperm, int Cin, int Cout, hipStream_t s);
-
 // fnp_spconv_forward for f32 3x3x3 SubM layers (16 / 32 / 64 / 128 channels in = out) on the class-sorted row order: same bits
 extern "C" int fnp_spconv_forward_f32_sorted(const void *feat_in, int n_in_rows, const void *weight, const int *nbr, int nbr_stride, const int *perm,
                                              const int *n_out, int cap_out, void *feat_out, const float *scale, const float *shift,
                                              const void *residual, int relu, int wperm, int Cin, int Cout, fnp_stream_t stream) {
-    if (!feat_in || !weight || !nbr || !perm || !n_out || !feat_out || cap_out <= 0 || nbr_stride < cap_out || n_in_rows <= 0) return FNP_ERR_ARG;
-    if ((scale == nullptr) != (shift == nullptr) || Cin != Cout) return FNP_ERR_ARG;
-    const long long xb = (long long)n_in_rows * Cin * 4;
-    if (xb >= 0x7fffffffll) return FNP_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-#define FNP_SCASE(C)                                                                                                              \
-    if (Cin == C)                                                                                                                 \
-        return launch_f32<C, C>(feat_in, xb, weight, nbr, nbr_stride, 27, n_out, cap_out, feat_out, scale, shift, residual, relu, \
-                                wperm != 0, s, perm);
-    FNP_SCASE(16)
-    FNP_SCASE(32)
-    FNP_SCASE(64)
-    FNP_SCASE(128)
-#undef FNP_SCASE
-    return FNP_ERR_ARG;
+    const ConvArgs a{feat_in, (long long)n_in_rows * Cin * 4, weight, nbr, nbr_stride, 27, n_out, cap_out, feat_out, scale, shift, residual, relu, 0,
+                     (hipStream_t)stream};
+    if (!fnp_conv_args_ok(a, n_in_rows) || !perm) return FNP_ERR_ARG;
+    int rc = FNP_ERR_ARG;
+    if (fnp_fits32(a.x_bytes))
+        fnp_for_pair(Cin, Cout, rc, F32SortedPairs{}, [&](auto p) { return launch_f32<decltype(p)::ci, decltype(p)::co>(a, wperm != 0, perm); });
+    return rc;
 }
 
 // f32 in / f32 out on the matrix pipe; FNP_ERR_ARG when the shape is not built (the caller falls back to the VALU chain)
-int fnp_spconv_forward_f32_mfma(const void *feat_in, long long n_in_rows, const void *weight, const int *nbr, int nbr_stride,
-                                int K, const int *n_out, int cap_out, void *feat_out, const float *scale, const float *shift,
-                                const void *residual, int relu, int wperm, int Cin, int Cout, hipStream_t s) {
-    const long long xb = n_in_rows * Cin * 4;
-    if (xb <= 0 || xb >= 0x7fffffffll || (long long)K * Cin * Cout * 4 >= 0x7fffffffll) return FNP_ERR_ARG;
-#define FNP_CASE(CI, CO)              \
-    if (Cin == CI && Cout == CO)      \
-        return launch_f32<CI, CO>(feat_in, xb, weight, nbr, nbr_stride, K, n_out, cap_out, feat_out, scale, shift, residual, relu, wperm != 0, s);
-    FNP_CASE(16, 16)
-    FNP_CASE(16, 32)
-    FNP_CASE(32, 32)
-    FNP_CASE(32, 64)
-    FNP_CASE(64, 64)
-    FNP_CASE(64, 128)
-    FNP_CASE(128, 128)
-    // transposed channel pairs: the data gradients of the three channel-doubling convolutions
-    FNP_CASE(32, 16)
-    FNP_CASE(64, 32)
-    FNP_CASE(128, 64)
-#undef FNP_CASE
-    return FNP_ERR_ARG;
+int fnp_spconv_forward_f32_mfma(const ConvArgs &a, int wperm, int Cin, int Cout) {
+    int rc = FNP_ERR_ARG;
+    if (fnp_fits32(a.x_bytes) && fnp_fits32((long long)a.K * Cin * Cout * 4))
+        fnp_for_pair(Cin, Cout, rc, ConvPairs{}, [&](auto p) { return launch_f32<decltype(p)::ci, decltype(p)::co>(a, wperm != 0); });
+    return rc;
 }

@@ -216,30 +216,22 @@ __global__ __launch_bounds__(kO128NT, 2) void spconv_out128_kernel(const TAct *_
 }
 
 template <typename TAct, typename TOut>
-int launch_out128(const void *x, int x_bytes, const void *w, const int *nbr, int nbr_stride, const int *n_out, int cap, void *y, const float *scale,
-                  const float *shift, int relu, hipStream_t s) {
+int launch_out128(const ConvArgs &a) {
     auto kern = spconv_out128_kernel<TAct, TOut>;
-    static bool raised = false;   // (idempotent; a race only repeats the call)
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kO128Lds) != hipSuccess) return FNP_ERR_HIP;
-        raised = true;
-    }
+    static bool raised = false;
+    if (const int rc = fnp_raise_lds(reinterpret_cast<const void *>(kern), kO128Lds, raised)) return rc;
     // persistent grid, one workgroup per CU (its LDS admits no second one); the kernel cuts the rows evenly over the grid's waves
-    hipLaunchKernelGGL(kern, dim3(256), dim3(kO128NT), kO128Lds, s, (const TAct *)x, x_bytes, (const TAct *)w, nbr, nbr_stride, n_out, cap, (TOut *)y, scale,
-                       shift, relu);
+    hipLaunchKernelGGL(kern, dim3(256), dim3(kO128NT), kO128Lds, a.stream, (const TAct *)a.x, (int)a.x_bytes, (const TAct *)a.w, a.nbr, a.nbr_stride, a.n_out,
+                       a.cap, (TOut *)a.y, a.scale, a.shift, a.relu);
     FNP_LAUNCH_CHECK();
     return FNP_OK;
 }
 
 }  // namespace
 
-int fnp_launch_out128(int in_dtype, int out_f32, const void *x, int x_bytes, const void *w, const int *nbr, int nbr_stride, const int *n_out, int cap, void *y,
-                      const float *scale, const float *shift, int relu, hipStream_t s) {
-    if (in_dtype == FNP_BF16)
-        return out_f32 ? launch_out128<__bf16, float>(x, x_bytes, w, nbr, nbr_stride, n_out, cap, y, scale, shift, relu, s)
-                       : launch_out128<__bf16, __bf16>(x, x_bytes, w, nbr, nbr_stride, n_out, cap, y, scale, shift, relu, s);
-    if (in_dtype == FNP_F16)
-        return out_f32 ? launch_out128<_Float16, float>(x, x_bytes, w, nbr, nbr_stride, n_out, cap, y, scale, shift, relu, s)
-                       : launch_out128<_Float16, _Float16>(x, x_bytes, w, nbr, nbr_stride, n_out, cap, y, scale, shift, relu, s);
-    return FNP_ERR_ARG;
+int fnp_launch_out128(int in_dtype, int out_f32, const ConvArgs &a) {
+    return fnp_dispatch16(in_dtype, [&](auto t) {
+        using T = typename decltype(t)::type;
+        return out_f32 ? launch_out128<T, float>(a) : launch_out128<T, T>(a);
+    });
 }

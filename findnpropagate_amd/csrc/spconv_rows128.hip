@@ -396,26 +396,19 @@ __global__ __launch_bounds__(kR128NT, 2) void spconv_rows128_kernel(const TAct *
 }
 
 template <typename TAct>
-int launch_rows128(const void *x, const void *w, const int *nbr, int nbr_stride, const int *n_out, int cap, void *y, const float *scale,
-                   const float *shift, const void *residual, int relu, const SortedRb &srb, int grid, hipStream_t s) {
+int launch_rows128(const ConvArgs &a, const SortedRb &srb, int grid) {
     auto kern = spconv_rows128_kernel<TAct>;
-    static bool raised = false;   // (idempotent; a race only repeats the call)
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kR128Lds) != hipSuccess) return FNP_ERR_HIP;
-        raised = true;
-    }
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(kR128NT), kR128Lds, s, (const TAct *)x, (const TAct *)w, nbr, nbr_stride, n_out, cap, (TAct *)y, scale, shift,
-                       (const TAct *)residual, relu, srb);
+    static bool raised = false;
+    if (const int rc = fnp_raise_lds(reinterpret_cast<const void *>(kern), kR128Lds, raised)) return rc;
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(kR128NT), kR128Lds, a.stream, (const TAct *)a.x, (const TAct *)a.w, a.nbr, a.nbr_stride, a.n_out, a.cap,
+                       (TAct *)a.y, a.scale, a.shift, (const TAct *)a.residual, a.relu, srb);
     FNP_LAUNCH_CHECK();
     return FNP_OK;
 }
 
 }  // namespace
 
-int fnp_launch_rows128(int dtype, const void *x, const void *w, const int *nbr, int nbr_stride, const int *n_out, int cap, void *y, const float *scale,
-                       const float *shift, const void *residual, int relu, const int *perm, const unsigned *blockmask, int grid, hipStream_t s) {
+int fnp_launch_rows128(int dtype, const ConvArgs &a, const int *perm, const unsigned *blockmask, int grid) {
     const SortedRb srb{perm, blockmask};
-    if (dtype == FNP_BF16) return launch_rows128<__bf16>(x, w, nbr, nbr_stride, n_out, cap, y, scale, shift, residual, relu, srb, grid, s);
-    if (dtype == FNP_F16) return launch_rows128<_Float16>(x, w, nbr, nbr_stride, n_out, cap, y, scale, shift, residual, relu, srb, grid, s);
-    return FNP_ERR_ARG;
+    return fnp_dispatch16(dtype, [&](auto t) { return launch_rows128<typename decltype(t)::type>(a, srb, grid); });
 }

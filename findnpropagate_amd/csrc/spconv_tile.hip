@@ -23,6 +23,7 @@
 // Products, their order (offsets ascending, one 32-wide MFMA step per offset) and the epilogue arithmetic are those of
 // spconv_mfma_kernel: the output is bit-identical (tests/test_gpu_spconv.py::test_tile_kernel_equals_gather_kernel).
 #include "tilerb.h"
+#include "conv_launch.h"   // ConvArgs, the shared refusals and dispatch idioms
 #include <type_traits>
 
 // Instruments (development builds only; the shipped library has neither):
@@ -879,38 +880,35 @@ __global__ __launch_bounds__(256, 2) void spconv_tile64_kernel(const TAct *__res
 constexpr int kLds64 = 2 * 64 * 8 * 16 + (G64::WIN + G64::OVF + 1) * G64::ROWB + kK * G64::TILE * 2 + 16 + G64::OVF * 4 + 2 * 64 * 4;
 static_assert(2 * kLds64 <= 160 * 1024, "two workgroups per CU");
 
-template <typename TAct, bool X3 = false>
-int launch_tile64(const void *x, long long x_bytes, const void *w, const void *tile_rb, long long rb_bytes, const int *nbr, int nbr_stride,
-                  const int *n_out, int cap, void *y, const float *scale, const float *shift, const void *residual, int relu, hipStream_t s,
-                  X3Args x3 = X3Args{nullptr, nullptr, nullptr, nullptr, nullptr}) {
+// the tile rulebook of a launch and the split outputs of its X3 form
+struct TileRb {
+    const void *rb;
+    long long bytes;
+};
+constexpr X3Args kNoX3{nullptr, nullptr, nullptr, nullptr, nullptr};
+
+template <typename TAct, bool X3>
+int launch_tile64(const ConvArgs &a, const TileRb &t, const X3Args &x3) {
     auto kern = spconv_tile64_kernel<TAct, X3>;
-    static bool raised = false;   // (idempotent; a race only repeats the call)
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLds64) != hipSuccess) return FNP_ERR_HIP;
-        raised = true;
-    }
-    const int tiles = fnp_divup(cap, G64::TILE);
+    static bool raised = false;
+    if (const int rc = fnp_raise_lds(reinterpret_cast<const void *>(kern), kLds64, raised)) return rc;
+    const int tiles = fnp_divup(a.cap, G64::TILE);
     const int grid = tiles < 512 ? tiles : 512;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), kLds64, s, (const TAct *)x, (int)x_bytes, (const TAct *)w, (const unsigned char *)tile_rb, (int)rb_bytes,
-                       nbr, nbr_stride, n_out, cap, (TAct *)y, scale, shift, (const TAct *)residual, relu, x3);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3(256), kLds64, a.stream, (const TAct *)a.x, (int)a.x_bytes, (const TAct *)a.w, (const unsigned char *)t.rb, (int)t.bytes,
+                       a.nbr, a.nbr_stride, a.n_out, a.cap, (TAct *)a.y, a.scale, a.shift, (const TAct *)a.residual, a.relu, x3);
     FNP_LAUNCH_CHECK();
     return FNP_OK;
 }
 
-template <typename TAct, bool X3 = false>
-int launch_tile32(const void *x, long long x_bytes, const void *w, const void *tile_rb, long long rb_bytes, const int *nbr, int nbr_stride,
-                  const int *n_out, int cap, void *y, const float *scale, const float *shift, const void *residual, int relu, hipStream_t s,
-                  X3Args x3 = X3Args{nullptr, nullptr, nullptr, nullptr, nullptr}) {
+template <typename TAct, bool X3>
+int launch_tile32(const ConvArgs &a, const TileRb &t, const X3Args &x3) {
     auto kern = spconv_tile32_kernel<TAct, X3>;
-    static bool raised = false;   // (idempotent; a race only repeats the call)
-    if (!raised) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, kLds) != hipSuccess) return FNP_ERR_HIP;
-        raised = true;
-    }
-    const int tiles = fnp_divup(cap, kTile);
+    static bool raised = false;
+    if (const int rc = fnp_raise_lds(reinterpret_cast<const void *>(kern), kLds, raised)) return rc;
+    const int tiles = fnp_divup(a.cap, kTile);
     const int grid = tiles < 256 ? tiles : 256;
-    hipLaunchKernelGGL(kern, dim3(grid), dim3((kNCW + kNPW) * 64), kLds, s, (const TAct *)x, (int)x_bytes, (const TAct *)w, (const unsigned char *)tile_rb, (int)rb_bytes,
-                       nbr, nbr_stride, n_out, cap, (TAct *)y, scale, shift, (const TAct *)residual, relu, x3);
+    hipLaunchKernelGGL(kern, dim3(grid), dim3((kNCW + kNPW) * 64), kLds, a.stream, (const TAct *)a.x, (int)a.x_bytes, (const TAct *)a.w, (const unsigned char *)t.rb,
+                       (int)t.bytes, a.nbr, a.nbr_stride, a.n_out, a.cap, (TAct *)a.y, a.scale, a.shift, (const TAct *)a.residual, a.relu, x3);
     FNP_LAUNCH_CHECK();
     return FNP_OK;
 }
@@ -1025,46 +1023,37 @@ extern "C" int fnp_tile_rulebook_build(const int *nbr, int nbr_stride, int K, co
     return FNP_OK;
 }
 
+// fnp_spconv_forward_tiled and its split twin: the shared refusals, then the 32- or 64-channel kernel (x3: the split form's outputs, y
+// and residual of `a` null then)
+template <bool X3>
+static int forward_tiled(const ConvArgs &a, int dtype, int n_in_rows, const void *tile_rb, const void *feat_out, const void *residual, int Cin, int Cout,
+                         const X3Args &x3) {
+    if (!fnp_conv_args_ok(a, n_in_rows, true, false) || !tile_rb || Cin != Cout || (Cin != 32 && Cin != 64)) return FNP_ERR_ARG;
+    const TileRb t{tile_rb, fnp_tile_rulebook_bytes(a.cap, Cin)};
+    // 32-bit buffer offsets into the features, the int32 table (escape fetches) and the tile rulebook
+    if (!fnp_fits32(a.x_bytes) || !fnp_fits32((long long)kK * a.nbr_stride * 4) || !fnp_fits32(t.bytes)) return FNP_ERR_ARG;
+    if (!fnp_aligned(15, tile_rb, a.x, feat_out, a.w, residual)) return FNP_ERR_ARG;
+    return fnp_dispatch16(dtype, [&](auto tag) {
+        using T = typename decltype(tag)::type;
+        return Cin == 32 ? launch_tile32<T, X3>(a, t, x3) : launch_tile64<T, X3>(a, t, x3);
+    });
+}
+
 extern "C" int fnp_spconv_forward_tiled(const void *feat_in, int dtype, int n_in_rows, const void *weight, const void *tile_rb, const int *nbr,
                                         int nbr_stride, const int *n_out, int cap_out, void *feat_out, const float *scale, const float *shift,
                                         const void *residual, int relu, int Cin, int Cout, fnp_stream_t stream) {
-    if (!feat_in || !weight || !tile_rb || !nbr || !n_out || !feat_out || cap_out <= 0 || nbr_stride < cap_out || n_in_rows <= 0) return FNP_ERR_ARG;
-    if ((scale == nullptr) != (shift == nullptr) || Cin != Cout || (Cin != 32 && Cin != 64)) return FNP_ERR_ARG;
-    const long long xb = (long long)n_in_rows * Cin * 2, rbb = fnp_tile_rulebook_bytes(cap_out, Cin);
-    // 32-bit buffer offsets into the features, the int32 table (escape fetches) and the tile rulebook
-    if (xb >= 0x7fffffffll || (long long)kK * nbr_stride * 4 >= 0x7fffffffll || rbb >= 0x7fffffffll) return FNP_ERR_ARG;
-    if (((uintptr_t)tile_rb & 15) || ((uintptr_t)feat_in & 15) || ((uintptr_t)feat_out & 15) || ((uintptr_t)weight & 15) || ((uintptr_t)residual & 15)) return FNP_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    if (Cin == 32) {
-        if (dtype == FNP_BF16) return launch_tile32<__bf16>(feat_in, xb, weight, tile_rb, rbb, nbr, nbr_stride, n_out, cap_out, feat_out, scale, shift, residual, relu, s);
-        if (dtype == FNP_F16) return launch_tile32<_Float16>(feat_in, xb, weight, tile_rb, rbb, nbr, nbr_stride, n_out, cap_out, feat_out, scale, shift, residual, relu, s);
-    } else {
-        if (dtype == FNP_BF16) return launch_tile64<__bf16>(feat_in, xb, weight, tile_rb, rbb, nbr, nbr_stride, n_out, cap_out, feat_out, scale, shift, residual, relu, s);
-        if (dtype == FNP_F16) return launch_tile64<_Float16>(feat_in, xb, weight, tile_rb, rbb, nbr, nbr_stride, n_out, cap_out, feat_out, scale, shift, residual, relu, s);
-    }
-    return FNP_ERR_ARG;
+    if (!feat_out) return FNP_ERR_ARG;
+    const ConvArgs a{feat_in, (long long)n_in_rows * Cin * 2, weight, nbr, nbr_stride, kK, n_out, cap_out, feat_out, scale, shift, residual, relu, 0,
+                     (hipStream_t)stream};
+    return forward_tiled<false>(a, dtype, n_in_rows, tile_rb, feat_out, residual, Cin, Cout, kNoX3);
 }
 
 extern "C" int fnp_spconv_forward_tiled_split(const void *feat_in, int dtype, int n_in_rows, const void *weight, const void *tile_rb, const int *nbr,
                                               int nbr_stride, const int *n_out, int cap_out, float *feat_out, const float *scale, const float *shift,
                                               const float *residual, const void *addend, int relu, int Cin, int Cout, void *out_hi, void *out_lo,
                                               fnp_stream_t stream) {
-    if (!feat_in || !weight || !tile_rb || !nbr || !n_out || !out_hi || !out_lo || cap_out <= 0 || nbr_stride < cap_out || n_in_rows <= 0)
-        return FNP_ERR_ARG;   // (feat_out may be null: only the split is written)
-    if ((scale == nullptr) != (shift == nullptr) || Cin != Cout || (Cin != 32 && Cin != 64)) return FNP_ERR_ARG;
-    const long long xb = (long long)n_in_rows * Cin * 2, rbb = fnp_tile_rulebook_bytes(cap_out, Cin);
-    if (xb >= 0x7fffffffll || (long long)kK * nbr_stride * 4 >= 0x7fffffffll || rbb >= 0x7fffffffll) return FNP_ERR_ARG;
-    if (((uintptr_t)tile_rb & 15) || ((uintptr_t)feat_in & 15) || ((uintptr_t)feat_out & 15) || ((uintptr_t)weight & 15) || ((uintptr_t)residual & 15) ||
-        (((uintptr_t)addend | (uintptr_t)out_hi | (uintptr_t)out_lo) & 7))
-        return FNP_ERR_ARG;
-    hipStream_t s = (hipStream_t)stream;
-    const X3Args x3{residual, addend, feat_out, out_hi, out_lo};
-    if (Cin == 32) {
-        if (dtype == FNP_BF16) return launch_tile32<__bf16, true>(feat_in, xb, weight, tile_rb, rbb, nbr, nbr_stride, n_out, cap_out, nullptr, scale, shift, nullptr, relu, s, x3);
-        if (dtype == FNP_F16) return launch_tile32<_Float16, true>(feat_in, xb, weight, tile_rb, rbb, nbr, nbr_stride, n_out, cap_out, nullptr, scale, shift, nullptr, relu, s, x3);
-    } else {
-        if (dtype == FNP_BF16) return launch_tile64<__bf16, true>(feat_in, xb, weight, tile_rb, rbb, nbr, nbr_stride, n_out, cap_out, nullptr, scale, shift, nullptr, relu, s, x3);
-        if (dtype == FNP_F16) return launch_tile64<_Float16, true>(feat_in, xb, weight, tile_rb, rbb, nbr, nbr_stride, n_out, cap_out, nullptr, scale, shift, nullptr, relu, s, x3);
-    }
-    return FNP_ERR_ARG;
+    if (!out_hi || !out_lo || !fnp_aligned(7, addend, out_hi, out_lo)) return FNP_ERR_ARG;   // (feat_out may be null: only the split is written)
+    const ConvArgs a{feat_in, (long long)n_in_rows * Cin * 2, weight, nbr, nbr_stride, kK, n_out, cap_out, nullptr, scale, shift, nullptr, relu, 0,
+                     (hipStream_t)stream};
+    return forward_tiled<true>(a, dtype, n_in_rows, tile_rb, feat_out, residual, Cin, Cout, X3Args{residual, addend, feat_out, out_hi, out_lo});
 }
